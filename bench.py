@@ -11,6 +11,14 @@ Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 the
 script starts `torch.distributed.run --nproc-per-node N` as a child process
 (one rank per GPU, RCCL) unless it already runs under torch.distributed.run
 (WORLD_SIZE set, which must equal N).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line: the
+headline figure, the config, the HBM roofline of the same timings and the
+episode statistics the timed path gathers.  --full adds what takes work of its
+own: the CPU baseline (the oracle), the FP32 FLOP roofline from its work counts
+and the committed PMC figures of the loaded library.  --dump-outputs DIR writes
+what the last timed step returned (rank 0 writes DIR/<name>.npy, ranks r > 0
+DIR/<name>.rank<r>.npy).
 """
 from __future__ import annotations
 
@@ -246,6 +254,34 @@ def pmc_entry(workload: str, lib_path: str, path: str | None = None):
     return (entry if status == "current" else None), info
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays: dict, rank: int = 0, max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """Writes each array of `arrays` (name -> torch tensor whose first dim is
+    the env, or [rows, envs] for `episode_stats`) as float32 `<name>.npy`
+    under `dirname`.  When they exceed `max_bytes` in all, every array keeps
+    the same fixed sample of envs (a seeded permutation's first rows, sorted),
+    written as `env_index.npy` too.  Returns name -> shape."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in arrays.items()}
+    env_axis = {k: (1 if k == "episode_stats" else 0) for k in host}
+    total = sum(a.nbytes for a in host.values())
+    if total > max_bytes:
+        n_env = min(a.shape[env_axis[k]] for k, a in host.items())
+        per_env = sum(a.nbytes // a.shape[env_axis[k]] for k, a in host.items()) + 4
+        keep = max(1, min(n_env, max_bytes // per_env))
+        idx = np.sort(np.random.default_rng(0xD0).permutation(n_env)[:keep])
+        host = {k: np.ascontiguousarray(np.take(a, idx, axis=env_axis[k])) for k, a in host.items()}
+        host["env_index"] = idx.astype(np.float32 if n_env < (1 << 24) else np.float64)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for k, a in host.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), a)
+    return {k: list(a.shape) for k, a in host.items()}
+
+
 def launch_command(n: int, argv) -> list:
     """The child command of `bench.py --gpus N` (N > 1): torch.distributed.run
     with one process per GPU on this node, rendezvous on 127.0.0.1, each rank
@@ -268,7 +304,11 @@ def main():
     ap.add_argument("--env-id", default="PandaPush-v3")
     ap.add_argument("--batch", type=int, default=65536, help="envs per GPU")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the CPU baseline, the FP32 FLOP roofline and the committed PMC figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per env of the step kernel: 1, 8, 16, 0 = auto")
     ap.add_argument("--print-launch", action="store_true",
                     help="print the child command that --gpus N > 1 would start, and exit")
@@ -359,15 +399,27 @@ def main():
     kernel_ms = sum(s.elapsed_time(e) for s, e in zip(starts, stops)) / args.steps
     elapsed = max_over_ranks(elapsed, dev)
 
+    dumped = None
+    if args.dump_outputs and args.steps > 0:
+        # what a caller of the timed path holds after its last step: the views
+        # env.step(copy=False) returned and this rank's episode statistics
+        dumped = dump_outputs(args.dump_outputs, {
+            "observation": obs["observation"], "achieved_goal": obs["achieved_goal"],
+            "desired_goal": obs["desired_goal"], "reward": r, "terminated": te, "truncated": tr,
+            "final_observation": info["final_observation"], "final_achieved_goal": info["final_achieved_goal"],
+            "episode_stats": eps[1:]}, rank)
+
     total_env_steps = world * B * args.steps
     value = total_env_steps / elapsed
     bytes_env = algorithmic_bytes_per_env_step(env.obs_dim, env.action_dim, env.goal_dim, env.sim.cfg.n_objects)
     achieved = bytes_env * B / (kernel_ms * 1e-3) / 1e9
     workload = f"{args.env_id} x{B}/gpu"
-    from pandasim import _lib as _L
+    pmc, pmc_info = {}, None
+    if args.full:
+        from pandasim import _lib as _L
 
-    pmc, pmc_info = pmc_entry(workload, _L.LIB_PATH)
-    pmc = pmc or {}
+        pmc, pmc_info = pmc_entry(workload, _L.LIB_PATH)
+        pmc = pmc or {}
     out = {
         "metric": "env steps/sec (batched) PandaPush-v3 at 1/2/4/8 MI355X vs PyBullet CPU",
         "value": round(value, 1),
@@ -386,11 +438,16 @@ def main():
                    "global_batch": world * B, "substeps": 20, "parallelism": f"batch shard x{world}",
                    "lanes_per_env": env.lanes_per_env},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": pmc.get("bytes_per_launch"),
+                     "frac": round(achieved / HBM_PEAK_GBS, 6),
                      "kernel": f"k_step<{spec['task'].upper()},{spec['control_type'].upper()},{env.lanes_per_env}>",
                      "kernel_ms": round(kernel_ms, 4),
-                     "bytes_per_env_step": bytes_env, "pmc": pmc_info},
+                     "bytes_per_env_step": bytes_env},
     }
+    if args.full:
+        out["roofline"]["traffic"] = pmc.get("bytes_per_launch")
+        out["roofline"]["pmc"] = pmc_info
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     # The binding limit is VALU issue, not HBM: one wave per
     # SIMD at 65 536 envs (1 024 waves on 1 024 SIMDs) issues at most one VALU
     # instruction per 4 cycles (MI355X_MICROARCH.md, 'vector-instruction ISSUE
@@ -421,7 +478,9 @@ def main():
                            "last_success_rate": round(float(ep[1][done].mean()), 4) if done.any() else None,
                            "gathered_envs": int(ep.shape[1])}
         work = None
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full:
+            pass  # a plain run: the line above is all its headline figure needs
+        elif world == 1 and not args.no_cpu_baseline:
             work, out["cpu_baseline"] = cpu_baseline(spec["task"], args.cpu_seconds)
         else:
             # N > 1 (the CPU baseline is rank 0's at N = 1 only) or no CPU leg:

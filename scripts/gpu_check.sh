@@ -9,6 +9,8 @@ timeout -k 10 ${TEST_LIMIT:-900} python -u -m pytest tests -q -m gpu -rf --timeo
 rc=$?
 echo "[gpu_check] pytest rc=$rc"
 [ $rc -le 1 ] || exit $rc
-timeout -k 10 300 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || exit $?
+BENCH_OUT=${BENCH_OUT:-bench_out}  # where the full bench line goes
+mkdir -p "$BENCH_OUT"
+timeout -k 10 300 python bench.py --full > "$BENCH_OUT/bench.json" 2> "$BENCH_OUT/bench.err" || exit $?
 if [ -n "$AB" ]; then bash scripts/gpu_ab.sh || exit $?; fi
 echo "done rc=0"

@@ -2,7 +2,7 @@
 #   STAGES="tests smoke bench trace pmc phase" bash scripts/gpu_round.sh
 # tests  every -m gpu test (PYTEST_K narrows them)    -> gpurun_out/pytest_gpu.log
 # smoke  __graft_entry__.smoke()                      -> gpurun_out/smoke.log
-# bench  the default bench line with its CPU baseline -> gpurun_out/bench.json
+# bench  the --full bench line (with its CPU baseline) -> $BENCH_OUT/bench.json (default bench_out/)
 # trace  rocprofv3 --kernel-trace --stats of the bench command (ENV_ID, BATCH)
 # pmc    separate PMC passes of the same command: FETCH_SIZE, WRITE_SIZE, SQ counters
 # phase  per-phase cycle split of k_step (libpandasim_prof.so; PHASE_IDS)
@@ -26,7 +26,9 @@ if has smoke; then
   run timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
 fi
 if has bench; then
-  run timeout -k 10 300 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
+  BENCH_OUT=${BENCH_OUT:-bench_out}
+  mkdir -p "$BENCH_OUT"
+  run timeout -k 10 300 python bench.py --full > "$BENCH_OUT/bench.json" 2> "$BENCH_OUT/bench.err"
 fi
 cd /tmp
 if has trace; then

@@ -57,18 +57,67 @@ def test_bench_under_explicit_torchrun():
 
 
 def test_bench_single_rank_roofline_blocks():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4096",
-           "--cpu-seconds", "1.5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
+           "--batch", "4096", "--cpu-seconds", "1.5"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = _json_line(out.stdout)
     rf = line["roofline"]
+    assert rf["pmc"]["status"] in ("current", "stale", "missing")
     assert rf["bound"] == "hbm" and rf["bytes_per_env_step"] == 630 and 0 < rf["frac"] < 1
     fp = rf["fp32"]
     assert fp["flops_per_env_step"] > 1e5 and 0 < fp["frac"] < 1 and fp["peak_tflops"] == 157.3
     assert set(fp["split"]) == {"dynamics_and_rows", "pgs", "ik", "step"}
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run prints the headline line without the --full legs, and
+    --dump-outputs writes what its last timed step returned: the same arrays,
+    bit for bit, as the same envs, seeds and action stream stepped here (300
+    envs: several blocks and a ragged last one; 55 steps pass the TimeLimit of
+    50, so the auto-reset rows and the episode statistics are filled)."""
+    import numpy as np
+    import torch
+
+    import pandasim
+
+    B, W, K = 300, 2, 53
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+           "--batch", str(B), "--dump-outputs", str(d)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = _json_line(out.stdout)
+    assert line["steps"] == K and line["warmup"] == W and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["unit"] == "env-steps/s" and line["value"] > 0
+    # value = envs over one timed step's seconds (ms_per_step is rounded to 1e-4 ms: < 1 % of a step >= 10 us)
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / B - 1) < 1e-2
+    assert "cpu_baseline" not in line and "fp32" not in line["roofline"] and "pmc" not in line["roofline"]
+
+    dev = torch.device("cuda", 0)
+    env = pandasim.make("PandaPush-v3", num_envs=B, device=dev)
+    env.reset(seed=(12345 + np.arange(B)).astype("uint64"))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0xC0FFEE)
+    actions = torch.rand(W + K, B, env.action_dim, device=dev, generator=gen) * 2 - 1
+    eps = env.record_episode_statistics()
+    for k in range(W + K):
+        if k == W:
+            eps.zero_()
+        obs, r, te, tr, info = env.step(actions[k], copy=False)
+    want = {"observation": obs["observation"], "achieved_goal": obs["achieved_goal"],
+            "desired_goal": obs["desired_goal"], "reward": r, "terminated": te, "truncated": tr,
+            "final_observation": info["final_observation"], "final_achieved_goal": info["final_achieved_goal"],
+            "episode_stats": eps[1:]}
+    assert sorted(os.listdir(d)) == sorted(k + ".npy" for k in want)
+    assert set(line["dumped_outputs"]["arrays"]) == set(want)
+    for k, v in want.items():
+        got = np.load(d / (k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == tuple(v.shape), k
+        assert np.array_equal(got, v.float().cpu().numpy()), k
+    assert np.load(d / "episode_stats.npy")[2].sum() >= B  # every env finished an episode in the timed steps
 
 
 _RCCL_ONE_RANK = r"""

@@ -332,6 +332,41 @@ def test_bench_fp32_roofline_without_the_cpu_leg():
     assert bench.committed_work_counts("no such task") is None
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_above_the_cap(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every array as float32 .npy; above
+    the byte cap, one fixed sample of envs, the same for every array and from
+    call to call, named in env_index.npy."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    B = 1000
+    arrays = {"observation": torch.arange(B * 18, dtype=torch.float32).reshape(B, 18),
+              "terminated": (torch.arange(B) % 3 == 0).to(torch.uint8),
+              "episode_stats": torch.arange(3 * B, dtype=torch.float32).reshape(3, B)}
+    shapes = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert shapes == {"observation": [B, 18], "terminated": [B], "episode_stats": [3, B]}
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v.float().numpy())
+    cap = 40_000  # of 88 000 bytes
+    for d in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / d), arrays, max_bytes=cap)
+    idx = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy").astype(np.int64))
+    assert 0 < len(idx) < B and np.all(np.diff(idx) > 0) and shapes["observation"] == [len(idx), 18]
+    total = 0
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        want = v.float().numpy()
+        assert np.array_equal(got, want[:, idx] if k == "episode_stats" else want[idx]), k
+        total += got.nbytes
+    assert total + idx.size * 4 <= cap
+    bench.dump_outputs(str(tmp_path / "r"), arrays, rank=2)
+    assert sorted(os.listdir(tmp_path / "r")) == sorted(k + ".rank2.npy" for k in arrays)
+
+
 def test_rim_point_culling_skips_only_invalid_candidates():
     """BoxCyl::visit (csrc/ps_physics.h) skips a cap's rim points for a wave
     when no lane's box reaches within the margin (+0.1 mm) of the cap's plane

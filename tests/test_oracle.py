@@ -547,3 +547,46 @@ def test_resting_object_normal_impulses_carry_its_weight(task):
     assert np.all(np.abs(np.array(env.obj[0].pos) - p) < 1e-4)
     assert abs(env.obj[0].pos[2] - p[2]) < 1e-8
     assert np.all(np.abs(np.array(env.obj[0].vel)) < 1e-4)
+
+
+# ------------------------------------------------- link velocities vs positions
+def test_link_velocities_are_the_derivative_of_the_link_pose():
+    """po_link_state's v and omega against central differences of its own COM
+    position and orientation along q +- h qd (h = 1e-6), on all 12 links and
+    the 256 configurations of helpers.link_sample: the analytic Jacobian
+    (point_jac, written side by side with the kernel's) is tied to the forward
+    kinematics alone.  omega = vee(Rdot R^T) with R from the returned
+    quaternions.
+
+    Measured: worst |v - dp/dt| 2.2e-10 m/s, worst |omega - vee| 7.1e-10 rad/s
+    (rounding 1e-16 / h and the h^2 truncation term); asserted 1e-7.  The
+    quaternions are unit to 3.4e-16.  The sample takes each getRotation branch at
+    least 24 times on every link >= 1 (link 0 turns about z only: trace > 0 and
+    i = 2), which tests/test_gpu_queries.py relies on."""
+    from helpers import NUM_LINKS, link_sample, oracle_link_states, quat_to_matrix, rotation_branch
+
+    cfg = kat_config()
+    q, qd = link_sample(256, 0)
+    h = 1e-6
+    worst_v = worst_w = worst_n = 0.0
+    for link in range(NUM_LINKS):
+        _, quat, v, w = oracle_link_states(cfg, q, qd, link)
+        pp, qp, _, _ = oracle_link_states(cfg, q + h * qd, qd, link)
+        pm, qm, _, _ = oracle_link_states(cfg, q - h * qd, qd, link)
+        worst_n = max(worst_n, np.abs(np.linalg.norm(quat, axis=1) - 1.0).max())
+        v_fd = (pp - pm) / (2 * h)
+        R = quat_to_matrix(quat)
+        W = (quat_to_matrix(qp) - quat_to_matrix(qm)) / (2 * h) @ np.swapaxes(R, -1, -2)
+        w_fd = 0.5 * np.stack([W[:, 2, 1] - W[:, 1, 2], W[:, 0, 2] - W[:, 2, 0], W[:, 1, 0] - W[:, 0, 1]], -1)
+        worst_v = max(worst_v, np.abs(v - v_fd).max())
+        worst_w = max(worst_w, np.abs(w - w_fd).max())
+        branch, _ = rotation_branch(R)
+        counts = np.bincount(branch, minlength=4)
+        if link >= 1:
+            assert counts.min() >= 24, (link, counts)
+        else:
+            assert counts[3] > 0 and counts[2] > 0 and counts[0] == counts[1] == 0, counts
+    print(f"link velocity vs finite differences: v {worst_v:.3g} m/s, omega {worst_w:.3g} rad/s, "
+          f"| |quat| - 1 | {worst_n:.3g}")
+    assert worst_v < 1e-7 and worst_w < 1e-7
+    assert worst_n < 1e-12

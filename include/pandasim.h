@@ -159,6 +159,32 @@ int ps_step(ps_ctx *ctx, void *state, const float *actions, float *obs, float *a
             uint8_t *terminated, uint8_t *truncated, int autoreset, float *final_obs, float *final_ag,
             void *stream);
 
+/* ps_step with a target orientation of the end effector per env: the fused
+ * step of Panda.set_action(action, euler_xyz) (panda_ori.py:52-99).  orn:
+ * device [B, 4] f32 quaternions (x, y, z, w), which calculateInverseKinematics
+ * receives in place of panda.py:89's standard (1, 0, 0, 0) and normalises;
+ * every other argument, the 20 substeps, observation, reward, TimeLimit,
+ * auto-reset, the non-finite guard, the episode statistics, the lanes-per-env
+ * choice (ps_set_lanes_per_env, ps_step_lanes) and the motor-row bookkeeping
+ * are ps_step's.  orn == NULL: PS_ERR_ARG.  A joints-control context:
+ * PS_ERR_UNSUPPORTED (the reference ignores euler_xyz there: call ps_step). */
+int ps_step_oriented(ps_ctx *ctx, void *state, const float *actions, const float *orn, float *obs, float *ag,
+                     float *dg, float *reward, uint8_t *terminated, uint8_t *truncated, int autoreset,
+                     float *final_obs, float *final_ag, void *stream);
+
+/* scipy's Rotation.from_euler('xyz', e, degrees=True).as_quat() (panda_ori.py:91:
+ * extrinsic rotations about x, y, then z) for n rows: euler_deg device [n, 3]
+ * f32 degrees -> quat device [n, 4] f32 (x, y, z, w; the sign is not
+ * canonicalised).  fp64 arithmetic, rounded once to f32. */
+int ps_euler_xyz_to_quat(ps_ctx *ctx, const float *euler_deg, float *quat, int64_t n, void *stream);
+
+/* Rotation.from_quat(q).as_euler('xyz', degrees=True) (panda_cartesian.py:222-225)
+ * for n rows: quat device [n, 4] f32 (x, y, z, w; normalised first) ->
+ * euler_deg device [n, 3] f32 degrees, x and z angles in [-180, 180], y angle
+ * in [-90, 90].  fp64 arithmetic, rounded once to f32.  Within 1e-3 degrees of
+ * pitch +-90 (gimbal lock) the result is unspecified. */
+int ps_quat_to_euler_xyz(ps_ctx *ctx, const float *quat, float *euler_deg, int64_t n, void *stream);
+
 /* Lanes per env of ps_step's kernel: 1 (one env per lane, the large-batch
  * kernel), 16 or 8 (a group of 16 or 8 lanes shares each env's constraint
  * solve -- the small-batch kernels, one object at most: not Stack); 0

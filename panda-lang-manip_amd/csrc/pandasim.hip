@@ -260,6 +260,46 @@ __global__ __launch_bounds__(256) void k_compute_reward(int task, int reward_typ
 }
 
 
+// scipy's Rotation.from_euler('xyz', e, degrees=True).as_quat() (panda_ori.py:91):
+// extrinsic rotations about x, then y, then z, q = qz qy qx as (x, y, z, w).
+// One lane per row, fp64 arithmetic, rounded once to f32 on store.
+__global__ __launch_bounds__(256) void k_euler_xyz_to_quat(const float *euler_deg, float *quat, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr double half_rad = 3.14159265358979323846 / 180.0 * 0.5;
+    double sa, ca, sb, cb, sc, cc;
+    sincos((double)euler_deg[i * 3] * half_rad, &sa, &ca);
+    sincos((double)euler_deg[i * 3 + 1] * half_rad, &sb, &cb);
+    sincos((double)euler_deg[i * 3 + 2] * half_rad, &sc, &cc);
+    quat[i * 4] = (float)(sa * cb * cc - ca * sb * sc);
+    quat[i * 4 + 1] = (float)(ca * sb * cc + sa * cb * sc);
+    quat[i * 4 + 2] = (float)(ca * cb * sc - sa * sb * cc);
+    quat[i * 4 + 3] = (float)(ca * cb * cc + sa * sb * sc);
+}
+
+// Rotation.from_quat(q).as_euler('xyz', degrees=True) (panda_cartesian.py:222-225):
+// q is normalised first; angles about x and z in [-180, 180], about y in
+// [-90, 90].  Within 1e-3 deg of pitch +-90 (gimbal lock: the x and z angles
+// are not separately determined) the result is unspecified.
+__global__ __launch_bounds__(256) void k_quat_to_euler_xyz(const float *quat, float *euler_deg, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double x = quat[i * 4], y = quat[i * 4 + 1], z = quat[i * 4 + 2], w = quat[i * 4 + 3];
+    const double inv = 1.0 / sqrt(x * x + y * y + z * z + w * w);
+    x *= inv; y *= inv; z *= inv; w *= inv;
+    // R = Rz(c) Ry(b) Rx(a): R20 = -sin b, R21 = cos b sin a, R22 = cos b cos a,
+    // R10 = cos b sin c, R00 = cos b cos c; b from atan2(sin b, |cos b|), which
+    // keeps its precision near +-90 where asin loses it
+    const double r21 = 2.0 * (y * z + w * x), r22 = 1.0 - 2.0 * (x * x + y * y);
+    const double r10 = 2.0 * (x * y + w * z), r00 = 1.0 - 2.0 * (y * y + z * z);
+    const double sb = 2.0 * (w * y - x * z);
+    constexpr double deg = 180.0 / 3.14159265358979323846;
+    euler_deg[i * 3] = (float)(atan2(r21, r22) * deg);
+    euler_deg[i * 3 + 1] = (float)(atan2(sb, sqrt(r21 * r21 + r22 * r22)) * deg);
+    euler_deg[i * 3 + 2] = (float)(atan2(r10, r00) * deg);
+}
+
+
 // ------------------------------------------------------------- rendering
 // Camera of a view/projection pair (column-major float[16], as getCameraImage
 // takes them): eye, the view axes (s, u, -f rows of the rotation) and the
@@ -748,21 +788,22 @@ int ps_reset(ps_ctx *c, void *state, const uint8_t *mask, const uint64_t *seeds,
     return check_launch(c);
 }
 
-int ps_step(ps_ctx *c, void *state, const float *actions, float *obs, float *ag, float *dg, float *reward,
-            uint8_t *terminated, uint8_t *truncated, int autoreset, float *final_obs, float *final_ag,
-            void *stream) {
-    if (!c || !state || !actions || !reward || !terminated || !truncated)
+// ps_step and ps_step_oriented (io.orn != NULL: ee control, checked by the
+// caller): one stash, lanes-per-env choice and gain-row bookkeeping
+static int step_with(ps_ctx *c, void *state, const ps_step_io &io, void *stream) {
+    if (!c || !state || !io.actions || !io.reward || !io.terminated || !io.truncated)
         return fail(c, PS_ERR_ARG, "null argument");
     if (!scene_matches_task(c->cfg)) return fail(c, PS_ERR_UNSUPPORTED, "scene does not match the task");
     hipStream_t st = (hipStream_t)stream;
     if (ensure_stash(c, st) != PS_OK) return fail(c, PS_ERR_HIP, "hipMalloc of the Stack stash failed");
-    const ps_step_io io{actions, obs, ag, dg, reward, terminated, truncated, final_obs, final_ag, autoreset};
     const int lanes = ps_step_lanes(c);
     const bool ee = c->cfg.control == PS_CONTROL_EE;
     int rc;
 #define PS_STEP_TASK_CASE(T)                                                                              \
     case T:                                                                                               \
-        rc = ee ? PS_STEP_LAUNCHER_NAME(T, 0)(c, state, io, lanes, st) : PS_STEP_LAUNCHER_NAME(T, 1)(c, state, io, lanes, st); \
+        rc = io.orn ? PS_STEP_ORI_LAUNCHER_NAME(T)(c, state, io, lanes, st)                               \
+             : ee   ? PS_STEP_LAUNCHER_NAME(T, 0)(c, state, io, lanes, st)                                \
+                    : PS_STEP_LAUNCHER_NAME(T, 1)(c, state, io, lanes, st);                               \
         break;
     switch (c->cfg.task) {
         PS_STEP_TASK_CASE(0) PS_STEP_TASK_CASE(1) PS_STEP_TASK_CASE(2)
@@ -775,6 +816,37 @@ int ps_step(ps_ctx *c, void *state, const float *actions, float *obs, float *ag,
         c->gains_state = state;
     }
     return rc;
+}
+
+int ps_step(ps_ctx *c, void *state, const float *actions, float *obs, float *ag, float *dg, float *reward,
+            uint8_t *terminated, uint8_t *truncated, int autoreset, float *final_obs, float *final_ag,
+            void *stream) {
+    const ps_step_io io{actions, obs, ag, dg, reward, terminated, truncated, final_obs, final_ag, autoreset, nullptr};
+    return step_with(c, state, io, stream);
+}
+
+int ps_step_oriented(ps_ctx *c, void *state, const float *actions, const float *orn, float *obs, float *ag,
+                     float *dg, float *reward, uint8_t *terminated, uint8_t *truncated, int autoreset,
+                     float *final_obs, float *final_ag, void *stream) {
+    if (!c || !orn) return fail(c, PS_ERR_ARG, "null argument");
+    if (c->cfg.control != PS_CONTROL_EE)
+        return fail(c, PS_ERR_UNSUPPORTED, "a target orientation needs ee control (joints control ignores it: ps_step)");
+    const ps_step_io io{actions, obs, ag, dg, reward, terminated, truncated, final_obs, final_ag, autoreset, orn};
+    return step_with(c, state, io, stream);
+}
+
+int ps_euler_xyz_to_quat(ps_ctx *c, const float *euler_deg, float *quat, int64_t n, void *stream) {
+    if (!c || !euler_deg || !quat || n < 0) return fail(c, PS_ERR_ARG, "bad argument");
+    if (n == 0) return PS_OK;
+    hipLaunchKernelGGL(k_euler_xyz_to_quat, grid_of(n, 256), dim3(256), 0, (hipStream_t)stream, euler_deg, quat, n);
+    return check_launch(c);
+}
+
+int ps_quat_to_euler_xyz(ps_ctx *c, const float *quat, float *euler_deg, int64_t n, void *stream) {
+    if (!c || !quat || !euler_deg || n < 0) return fail(c, PS_ERR_ARG, "bad argument");
+    if (n == 0) return PS_OK;
+    hipLaunchKernelGGL(k_quat_to_euler_xyz, grid_of(n, 256), dim3(256), 0, (hipStream_t)stream, quat, euler_deg, n);
+    return check_launch(c);
 }
 
 int ps_set_lanes_per_env(ps_ctx *c, int lanes) {

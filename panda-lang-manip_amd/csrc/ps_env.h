@@ -40,6 +40,7 @@ struct ps_step_io {
     uint8_t *terminated, *truncated;
     float *final_obs, *final_ag;
     int autoreset;
+    const float *orn;  // ps_step_oriented: [B, 4] target quaternions (x, y, z, w); NULL in ps_step
 };
 
 // one launcher per (task, control) pair (step_kernels.hip) and per scene
@@ -63,6 +64,20 @@ PS_DECLARE_STEP_GROUP_LAUNCHER(0, 0) PS_DECLARE_STEP_GROUP_LAUNCHER(0, 1) PS_DEC
 PS_DECLARE_STEP_GROUP_LAUNCHER(1, 1) PS_DECLARE_STEP_GROUP_LAUNCHER(2, 0) PS_DECLARE_STEP_GROUP_LAUNCHER(2, 1)
 PS_DECLARE_STEP_GROUP_LAUNCHER(3, 0) PS_DECLARE_STEP_GROUP_LAUNCHER(3, 1) PS_DECLARE_STEP_GROUP_LAUNCHER(5, 0)
 PS_DECLARE_STEP_GROUP_LAUNCHER(5, 1)
+// ps_step_oriented's kernels (k_step<..., ORI = true>, ee control only): the
+// same split, built from step_kernels.hip with -DPS_STEP_ORI=1
+#define PS_STEP_ORI_LAUNCHER_NAME_(T) ps_launch_step_ori_##T
+#define PS_STEP_ORI_LAUNCHER_NAME(T) PS_STEP_ORI_LAUNCHER_NAME_(T)
+#define PS_DECLARE_STEP_ORI_LAUNCHER(T) \
+    int PS_STEP_ORI_LAUNCHER_NAME(T)(ps_ctx * c, void *state, const ps_step_io &io, int lanes, hipStream_t st);
+PS_DECLARE_STEP_ORI_LAUNCHER(0) PS_DECLARE_STEP_ORI_LAUNCHER(1) PS_DECLARE_STEP_ORI_LAUNCHER(2)
+PS_DECLARE_STEP_ORI_LAUNCHER(3) PS_DECLARE_STEP_ORI_LAUNCHER(4) PS_DECLARE_STEP_ORI_LAUNCHER(5)
+#define PS_STEP_ORI_GROUP_LAUNCHER_NAME_(T) ps_launch_step_ori_groups_##T
+#define PS_STEP_ORI_GROUP_LAUNCHER_NAME(T) PS_STEP_ORI_GROUP_LAUNCHER_NAME_(T)
+#define PS_DECLARE_STEP_ORI_GROUP_LAUNCHER(T) \
+    int PS_STEP_ORI_GROUP_LAUNCHER_NAME(T)(ps_ctx * c, const void *params, const ps_step_io &io, int lanes, hipStream_t st);
+PS_DECLARE_STEP_ORI_GROUP_LAUNCHER(0) PS_DECLARE_STEP_ORI_GROUP_LAUNCHER(1) PS_DECLARE_STEP_ORI_GROUP_LAUNCHER(2)
+PS_DECLARE_STEP_ORI_GROUP_LAUNCHER(3) PS_DECLARE_STEP_ORI_GROUP_LAUNCHER(5)
 #define PS_SIM_LAUNCHER_NAME_(NOBJ, SHAPE) ps_launch_sim_step_##NOBJ##_##SHAPE
 #define PS_SIM_LAUNCHER_NAME(NOBJ, SHAPE) PS_SIM_LAUNCHER_NAME_(NOBJ, SHAPE)
 #define PS_DECLARE_SIM_LAUNCHER(NOBJ, SHAPE) \
@@ -518,9 +533,12 @@ PS_D void reset_env(float q[9], float qd[9], Body *bd, double g[6], Pcg &r, uint
     }
 }
 
-// Panda.set_action (panda.py:52-107) -> motor targets (control_joints)
-template <int CONTROL>
-PS_D void set_action(const KParams &P, const float *act, const float q[9], Motors &m) {
+// Panda.set_action (panda.py:52-107) -> motor targets (control_joints).
+// ORI (ee control; panda_ori.py:52-99): the IK target's orientation is the
+// env's quaternion orn[4] (x, y, z, w; inverse_kinematics normalises it) in
+// place of the standard one, which stays a compile-time constant otherwise.
+template <int CONTROL, bool ORI = false>
+PS_D void set_action(const KParams &P, const float *act, const float q[9], Motors &m, const float *orn = nullptr) {
     float a[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) a[j] = j < P.action_dim ? fminf(fmaxf(act[j], -1.0f), 1.0f) : 0.0f;
@@ -534,7 +552,10 @@ PS_D void set_action(const KParams &P, const float *act, const float q[9], Motor
         V3 t = p + mk(a[0] * 0.05f, a[1] * 0.05f, a[2] * 0.05f);
         t.z = fmaxf(0.0f, t.z);
         float qik[9];
-        inverse_kinematics<11>(q, t - P.sc.base, Q4{1.0f, 0.0f, 0.0f, 0.0f}, qik);
+        if constexpr (ORI)
+            inverse_kinematics<11>(q, t - P.sc.base, Q4{orn[0], orn[1], orn[2], orn[3]}, qik);
+        else
+            inverse_kinematics<11>(q, t - P.sc.base, Q4{1.0f, 0.0f, 0.0f, 0.0f}, qik);
 #pragma unroll
         for (int d = 0; d < 7; d++) tq[d] = qik[d];
     } else {
@@ -632,11 +653,14 @@ inline bool scene_matches_task(const ps_config &c) {
 // the 16 lanes of a group run the same setup and share the solver
 // (group_pgs); lane 0 of the group writes the env's results, and the groups
 // of the last wave past the batch end compute a copy of the last env and
-// write nothing.
-template <int TASK, int CONTROL, int G = 1>
+// write nothing.  ORI: ps_step_oriented's kernel, whose IK target takes env
+// i's orientation from orn [B, 4] (every lane of a group reads the same four
+// floats, as it does the action); ps_step's kernels never read orn.
+template <int TASK, int CONTROL, int G = 1, bool ORI = false>
 __global__ __launch_bounds__(kBlock, PS_STEP_MIN_WAVES) void k_step(KParams P, const float *actions, float *obs, float *ag, float *dg,
                                                  float *reward, uint8_t *terminated, uint8_t *truncated,
-                                                 float *final_obs, float *final_ag) {
+                                                 float *final_obs, float *final_ag, const float *orn) {
+    static_assert(!ORI || CONTROL == PS_CONTROL_EE, "a target orientation exists with ee control only");
     using T = TaskTraits<TASK>;
     const int64_t gi = ((int64_t)step_block<G>() * blockDim.x + threadIdx.x) / G;
     if (G == 1 && gi >= P.n) return;
@@ -658,7 +682,8 @@ __global__ __launch_bounds__(kBlock, PS_STEP_MIN_WAVES) void k_step(KParams P, c
     float tgt[9];
     {
         Motors m;
-        set_action<CONTROL>(P, actions + i * P.action_dim, q, m);
+        if constexpr (ORI) set_action<CONTROL, true>(P, actions + i * P.action_dim, q, m, orn + i * 4);
+        else set_action<CONTROL>(P, actions + i * P.action_dim, q, m);
         // every lane of a group stores the same targets (no lane reads a value
         // only another lane wrote; run_substeps reads them back for G > 1)
         if (G > 1 || writer) store_motor_targets(s, i, m);

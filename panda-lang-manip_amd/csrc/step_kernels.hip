@@ -4,7 +4,9 @@
 // jobs.  ps_step (pandasim.hip) calls the pair's launcher.  The one-lane
 // kernel and the launcher form one object; the 16- and 8-lane group kernels
 // form a second (-DPS_STEP_GROUPS=1), compiled with the same flags (-O3;
-// DESIGN.md §12.6).
+// DESIGN.md §12.6).  -DPS_STEP_ORI=1 (ee control only) builds the same two
+// objects of ps_step_oriented's kernels, k_step<..., ORI = true>, whose IK
+// target takes a per-env orientation.
 #include "ps_env.h"
 
 #ifdef PS_EXPERIMENT_G2
@@ -17,16 +19,28 @@
 #error "build with -DPS_STEP_TASK=<task> -DPS_STEP_CONTROL=<control>"
 #endif
 
-#define PS_LAUNCH(G)                                                                                               \
-    hipLaunchKernelGGL((k_step<PS_STEP_TASK, PS_STEP_CONTROL, G>), grid_of(P.n * (G), kBlock), dim3(kBlock), 0, st, \
-                       P, io.actions, io.obs, io.ag, io.dg, io.reward, io.terminated, io.truncated, io.final_obs,  \
-                       io.final_ag)
+#if defined(PS_STEP_ORI) && PS_STEP_ORI
+#if PS_STEP_CONTROL != 0  // PS_CONTROL_EE
+#error "-DPS_STEP_ORI=1 needs -DPS_STEP_CONTROL=0 (ee control)"
+#endif
+#define PS_ORI true
+#define PS_THIS_LAUNCHER PS_STEP_ORI_LAUNCHER_NAME(PS_STEP_TASK)
+#define PS_THIS_GROUP_LAUNCHER PS_STEP_ORI_GROUP_LAUNCHER_NAME(PS_STEP_TASK)
+#else
+#define PS_ORI false
+#define PS_THIS_LAUNCHER PS_STEP_LAUNCHER_NAME(PS_STEP_TASK, PS_STEP_CONTROL)
+#define PS_THIS_GROUP_LAUNCHER PS_STEP_GROUP_LAUNCHER_NAME(PS_STEP_TASK, PS_STEP_CONTROL)
+#endif
+
+#define PS_LAUNCH(G)                                                                                         \
+    hipLaunchKernelGGL((k_step<PS_STEP_TASK, PS_STEP_CONTROL, G, PS_ORI>), grid_of(P.n * (G), kBlock),       \
+                       dim3(kBlock), 0, st, P, io.actions, io.obs, io.ag, io.dg, io.reward, io.terminated,   \
+                       io.truncated, io.final_obs, io.final_ag, io.orn)
 
 #if defined(PS_STEP_GROUPS) && PS_STEP_GROUPS
 static_assert(PS_STEP_TASK != PS_TASK_STACK, "Stack has no group kernels (two objects: 21 DoFs)");
 
-int PS_STEP_GROUP_LAUNCHER_NAME(PS_STEP_TASK, PS_STEP_CONTROL)(ps_ctx *c, const void *params, const ps_step_io &io,
-                                                               int lanes, hipStream_t st) {
+int PS_THIS_GROUP_LAUNCHER(ps_ctx *c, const void *params, const ps_step_io &io, int lanes, hipStream_t st) {
     const KParams P = *static_cast<const KParams *>(params);
 #ifdef PS_EXPERIMENT_G2
     // two lanes per env, a measured experiment only
@@ -41,8 +55,7 @@ int PS_STEP_GROUP_LAUNCHER_NAME(PS_STEP_TASK, PS_STEP_CONTROL)(ps_ctx *c, const 
 }
 
 #else
-int PS_STEP_LAUNCHER_NAME(PS_STEP_TASK, PS_STEP_CONTROL)(ps_ctx *c, void *state, const ps_step_io &io, int lanes,
-                                                         hipStream_t st) {
+int PS_THIS_LAUNCHER(ps_ctx *c, void *state, const ps_step_io &io, int lanes, hipStream_t st) {
     KParams P = params_of(c, state);
     P.autoreset = io.autoreset;
     P.nonfinite = c->nonfinite;
@@ -53,7 +66,7 @@ int PS_STEP_LAUNCHER_NAME(PS_STEP_TASK, PS_STEP_CONTROL)(ps_ctx *c, void *state,
     // groups of 16 or 8 lanes per env exist for the one-object and robot-only tasks
 #if PS_STEP_TASK != 4  // PS_TASK_STACK
     if (lanes == 16 || lanes == 8 || (PS_G2_ENABLED && lanes == 2))
-        return PS_STEP_GROUP_LAUNCHER_NAME(PS_STEP_TASK, PS_STEP_CONTROL)(c, &P, io, lanes, st);
+        return PS_THIS_GROUP_LAUNCHER(c, &P, io, lanes, st);
 #endif
     PS_LAUNCH(1);
     return check_launch(c);

@@ -69,8 +69,13 @@ def exported_symbols():
         "ps_step", "ps_sim_step", "ps_link_state", "ps_inverse_kinematics", "ps_compute_reward", "ps_rng_seed",
         "ps_rng_uniform", "ps_rng_rotation", "ps_base_state", "ps_camera", "ps_render", "ps_deproject_image",
         "ps_deproject_pixels", "ps_set_nonfinite_guard", "ps_set_lanes_per_env", "ps_step_lanes",
-        "ps_mark_motor_rows_dirty", "ps_set_episode_stats",
+        "ps_mark_motor_rows_dirty", "ps_set_episode_stats", *ORIENTED_SYMBOLS,
     ]
+
+
+# added within ABI version 6: a library built before them (one of the two that
+# scripts/compare_libs.py loads) still binds; calling one on it raises AttributeError
+ORIENTED_SYMBOLS = ("ps_step_oriented", "ps_euler_xyz_to_quat", "ps_quat_to_euler_xyz")
 
 
 def check_fresh(path: str) -> None:
@@ -144,6 +149,12 @@ def lib():
     L.ps_deproject_image.argtypes = [V, V, D, I, I, V, V, V, V]
     L.ps_deproject_pixels.argtypes = [V, V, V, I, D, I, I, V, V]
     for name in exported_symbols():
+        if name in ORIENTED_SYMBOLS and "PANDASIM_LIB" in os.environ and not hasattr(L, name):
+            continue  # only a library named by PANDASIM_LIB may predate them
+        if name == "ps_step_oriented":
+            L.ps_step_oriented.argtypes = [V, V, V, V, V, V, V, V, V, V, I, V, V, V]
+        elif name in ORIENTED_SYMBOLS:
+            getattr(L, name).argtypes = [V, V, V, I64, V]
         getattr(L, name).restype = getattr(L, name).restype if name in ("ps_destroy", "ps_last_error") else I
     _lib = L
     return L

@@ -3,8 +3,9 @@
 The library is linked from parallel hipcc jobs (csrc/ps_env.h): the C ABI and
 small kernels (pandasim.hip), the fused step kernels of each (task, control)
 pair (step_kernels.hip: the one-lane kernel, 12 objects, and the 16/8-lane
-group kernels, 10 objects -- Stack has none) and the plugin-path substep kernel
-of each scene (sim_kernels.hip, 4 objects).
+group kernels, 10 objects -- Stack has none), the oriented step's kernels of
+each task at ee control (the same source with -DPS_STEP_ORI=1: 6 + 5 objects)
+and the plugin-path substep kernel of each scene (sim_kernels.hip, 4 objects).
 
 Every object is compiled with the same flags (-O3, no -mllvm scheduler
 options).  Round 3 built the group kernels at -O1 after an -O2/-O3 miscompute
@@ -54,6 +55,12 @@ UNITS = ([("pandasim", "pandasim.hip", [])]
          + [(f"step_t{t}_c{c}_groups", "step_kernels.hip",
              [f"-DPS_STEP_TASK={t}", f"-DPS_STEP_CONTROL={c}", "-DPS_STEP_GROUPS=1"])
             for t in range(6) if t != TASK_STACK for c in range(2)]
+         # ps_step_oriented's kernels (ee control only): 6 one-lane + 5 group objects
+         + [(f"step_ori_t{t}", "step_kernels.hip", [f"-DPS_STEP_TASK={t}", "-DPS_STEP_CONTROL=0", "-DPS_STEP_ORI=1"])
+            for t in range(6)]
+         + [(f"step_ori_t{t}_groups", "step_kernels.hip",
+             [f"-DPS_STEP_TASK={t}", "-DPS_STEP_CONTROL=0", "-DPS_STEP_ORI=1", "-DPS_STEP_GROUPS=1"])
+            for t in range(6) if t != TASK_STACK]
          + [(f"sim_{n}_{s}", "sim_kernels.hip", [f"-DPS_SIM_NOBJ={n}", f"-DPS_SIM_SHAPE={s}"])
             for n, s in ((0, 0), (1, 0), (1, 1), (2, 0))])
 

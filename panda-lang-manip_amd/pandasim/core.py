@@ -113,7 +113,9 @@ class PyBulletRobot(ABC):
 
     @abstractmethod
     def set_action(self, action: torch.Tensor) -> None:
-        """Set the [B, A] action. Must be called just before sim.step()."""
+        """Set the [B, A] action. Must be called just before sim.step().  A
+        robot that takes a target orientation (robots.Panda) adds an
+        ``euler_xyz=None`` argument (RobotTaskEnv.step passes it on)."""
 
     @abstractmethod
     def get_obs(self) -> torch.Tensor:
@@ -249,11 +251,16 @@ class RobotTaskEnv:
         self._saved_goal.pop(state_id)
         self.sim.remove_state(state_id)
 
-    def step(self, action) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, torch.Tensor,
-                                    Dict[str, Any]]:
-        """core.py:280-289."""
+    def step(self, action, euler_xyz=None) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor,
+                                                    torch.Tensor, Dict[str, Any]]:
+        """core.py:280-289; euler_xyz ([B, 3] or [3] degrees) goes to the
+        robot's set_action(action, euler_xyz) (panda_ori.py:52), and a robot
+        without that argument is called as before when it is None."""
         action = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(self.num_envs, -1)
-        self.robot.set_action(action)
+        if euler_xyz is None:
+            self.robot.set_action(action)
+        else:
+            self.robot.set_action(action, euler_xyz)
         self.sim.step()
         observation = self._get_obs()
         # An episode is terminated iff the agent has reached the target
@@ -296,8 +303,9 @@ class TimeLimit:
         self._elapsed.zero_()
         return self.env.reset(**kwargs)
 
-    def step(self, action):
-        obs, reward, terminated, truncated, info = self.env.step(action)
+    def step(self, action, euler_xyz=None):
+        obs, reward, terminated, truncated, info = (self.env.step(action) if euler_xyz is None
+                                                    else self.env.step(action, euler_xyz=euler_xyz))
         self._elapsed += 1
         truncated = truncated | (self._elapsed >= self.max_episode_steps)
         return obs, reward, terminated, truncated, info

@@ -115,19 +115,49 @@ class PandaVecEnv:
         info = {"is_success": self.compute_success(self._ag, self.sim.goals())}
         return self._obs_dict(), info
 
-    def step(self, actions, copy: bool = True) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor,
-                                                         torch.Tensor, Dict]:
+    def _target_orientation(self, euler_xyz, orientation) -> Optional[torch.Tensor]:
+        """step()'s target orientation as [B, 4] float32 quaternions (x, y, z, w),
+        or None for the standard one (ps_step).  With joints control both
+        arguments are ignored, as Panda.set_action does (panda_ori.py:55-60)."""
+        if euler_xyz is not None and orientation is not None:
+            raise ValueError("step: give euler_xyz or orientation, not both")
+        given, width, name = (euler_xyz, 3, "euler_xyz") if euler_xyz is not None else (orientation, 4, "orientation")
+        if given is None:
+            return None
+        t = torch.as_tensor(given, dtype=torch.float32)
+        if tuple(t.shape) not in ((width,), (self.num_envs, width)):
+            raise ValueError(f"step: {name} must have shape ({width},) or ({self.num_envs}, {width}), "
+                             f"got {tuple(t.shape)}")
+        if self.control_type != "ee":
+            return None
+        t = t.to(self.device).expand(self.num_envs, width).contiguous()
+        return self.sim.euler_xyz_to_quat(t) if width == 3 else t
+
+    def step(self, actions, copy: bool = True, euler_xyz=None, orientation=None) -> Tuple[
+            Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, torch.Tensor, Dict]:
         """RobotTaskEnv.step (core.py:280-289) + TimeLimit, fused in one kernel.
 
         copy=False returns views of the env's output buffers (valid until the
-        next step) and skips the clones."""
+        next step) and skips the clones.  euler_xyz ([B, 3] or [3] degrees,
+        scipy's extrinsic 'xyz') or orientation ([B, 4] or [4] quaternion
+        x, y, z, w) -- at most one of them -- is the end effector's target
+        orientation of this step (Panda.set_action(action, euler_xyz),
+        panda_ori.py:52-99; ps_step_oriented); with neither the target is the
+        standard (1, 0, 0, 0) of panda.py:89 (ps_step)."""
         if not self._has_reset:
             raise L.PandasimError("Cannot call env.step() before calling env.reset()")  # OrderEnforcing
+        orn = None if euler_xyz is None and orientation is None else self._target_orientation(euler_xyz, orientation)
         a = torch.as_tensor(actions, dtype=torch.float32, device=self.device).reshape(self.num_envs, self.action_dim)
         a = a.contiguous()
-        self.sim._call("ps_step", self.sim._ctx, _ptr(self.sim.state), _ptr(a), _ptr(self._obs), _ptr(self._ag),
-                       _ptr(self._dg), _ptr(self._reward), _ptr(self._term), _ptr(self._trunc), int(self.autoreset),
-                       _ptr(self._final_obs), _ptr(self._final_ag), self.sim._stream())
+        if orn is None:
+            self.sim._call("ps_step", self.sim._ctx, _ptr(self.sim.state), _ptr(a), _ptr(self._obs), _ptr(self._ag),
+                           _ptr(self._dg), _ptr(self._reward), _ptr(self._term), _ptr(self._trunc),
+                           int(self.autoreset), _ptr(self._final_obs), _ptr(self._final_ag), self.sim._stream())
+        else:
+            self.sim._call("ps_step_oriented", self.sim._ctx, _ptr(self.sim.state), _ptr(a), _ptr(orn),
+                           _ptr(self._obs), _ptr(self._ag), _ptr(self._dg), _ptr(self._reward), _ptr(self._term),
+                           _ptr(self._trunc), int(self.autoreset), _ptr(self._final_obs), _ptr(self._final_ag),
+                           self.sim._stream())
         if not copy:
             obs = {"observation": self._obs, "achieved_goal": self._ag, "desired_goal": self._dg}
             info = {"final_observation": self._final_obs, "final_achieved_goal": self._final_ag}

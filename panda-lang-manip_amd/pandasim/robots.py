@@ -1,4 +1,6 @@
-"""Batched Panda robot plugin (panda_gym/envs/robots/panda.py:10-140)."""
+"""Batched Panda robot plugin (panda_gym/envs/robots/panda.py:10-140), with the
+target orientation of panda_ori.py:52-99 (set_action(action, euler_xyz)) and
+get_ee_orientation of panda_cartesian.py:222-225."""
 from __future__ import annotations
 
 from typing import Optional
@@ -38,12 +40,14 @@ class Panda(PyBulletRobot):
         self.sim.set_spinning_friction(self.body_name, self.fingers_indices[0], spinning_friction=0.001)
         self.sim.set_spinning_friction(self.body_name, self.fingers_indices[1], spinning_friction=0.001)
 
-    def set_action(self, action: torch.Tensor) -> None:
-        """panda.py:52-70."""
+    def set_action(self, action: torch.Tensor, euler_xyz=None) -> None:
+        """panda.py:52-70; euler_xyz ([B, 3] or [3] degrees, scipy's extrinsic
+        'xyz'): the end effector's target orientation (panda_ori.py:52-70),
+        ignored with joints control."""
         action = torch.as_tensor(action, dtype=torch.float32, device=self.sim.device).clone()
         action = action.clamp(-1.0, 1.0)
         if self.control_type == "ee":
-            target_arm_angles = self.ee_displacement_to_target_arm_angles(action[:, :3])
+            target_arm_angles = self.ee_displacement_to_target_arm_angles(action[:, :3], euler_xyz)
         else:
             target_arm_angles = self.arm_joint_ctrl_to_target_arm_angles(action[:, :7])
         if self.block_gripper:
@@ -55,15 +59,19 @@ class Panda(PyBulletRobot):
         target_angles = torch.cat([target_arm_angles, half, half], dim=-1)
         self.control_joints(target_angles=target_angles)
 
-    def ee_displacement_to_target_arm_angles(self, ee_displacement: torch.Tensor) -> torch.Tensor:
-        """panda.py:72-92."""
+    def ee_displacement_to_target_arm_angles(self, ee_displacement: torch.Tensor, euler_xyz=None) -> torch.Tensor:
+        """panda.py:72-92; with euler_xyz, panda_ori.py:72-99."""
         ee_displacement = ee_displacement[:, :3] * 0.05  # limit maximum change in position
         ee_position = self.get_ee_position()
         target_ee_position = ee_position + ee_displacement
         # Clip the height target (panda.py:86)
         target_ee_position[:, 2] = target_ee_position[:, 2].clamp(min=0.0)
+        if euler_xyz is not None:
+            orientation = self.sim.euler_xyz_to_quat(euler_xyz)  # R.from_euler('xyz', e, degrees=True).as_quat()
+        else:
+            orientation = np.array([1.0, 0.0, 0.0, 0.0])
         target_arm_angles = self.inverse_kinematics(link=self.ee_link, position=target_ee_position,
-                                                    orientation=np.array([1.0, 0.0, 0.0, 0.0]))
+                                                    orientation=orientation)
         return target_arm_angles[:, :7]  # remove fingers angles
 
     def arm_joint_ctrl_to_target_arm_angles(self, arm_joint_ctrl: torch.Tensor) -> torch.Tensor:
@@ -96,6 +104,11 @@ class Panda(PyBulletRobot):
 
     def get_ee_position(self) -> torch.Tensor:
         return self.get_link_position(self.ee_link)
+
+    def get_ee_orientation(self) -> torch.Tensor:
+        """panda_cartesian.py:222-225: the ee link's orientation as [B, 3]
+        extrinsic 'xyz' Euler angles in degrees."""
+        return self.sim.quat_to_euler_xyz(self.get_link_orientation(self.ee_link))
 
     def get_ee_velocity(self) -> torch.Tensor:
         return self.get_link_velocity(self.ee_link)

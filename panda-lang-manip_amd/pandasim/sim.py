@@ -645,6 +645,29 @@ class PandaSim:
                    self._stream())
         return out
 
+    def euler_xyz_to_quat(self, euler_xyz) -> torch.Tensor:
+        """scipy's R.from_euler('xyz', e, degrees=True).as_quat() (panda_ori.py:91)
+        for (..., 3) degrees -> (..., 4) float32 (x, y, z, w), on the GPU."""
+        e = torch.as_tensor(euler_xyz, dtype=torch.float32, device=self.device)
+        if e.dim() == 0 or e.shape[-1] != 3:
+            raise ValueError(f"euler_xyz_to_quat: expected (..., 3) angles, got {tuple(e.shape)}")
+        flat = e.reshape(-1, 3).contiguous()
+        out = torch.empty(flat.shape[0], 4, device=self.device)
+        self._call("ps_euler_xyz_to_quat", self._ctx, _ptr(flat), _ptr(out), flat.shape[0], self._stream())
+        return out.reshape(*e.shape[:-1], 4)
+
+    def quat_to_euler_xyz(self, quat) -> torch.Tensor:
+        """R.from_quat(q).as_euler('xyz', degrees=True) (panda_cartesian.py:222-225)
+        for (..., 4) quaternions (x, y, z, w) -> (..., 3) float32 degrees, on
+        the GPU; unspecified within 1e-3 degrees of pitch +-90."""
+        q = torch.as_tensor(quat, dtype=torch.float32, device=self.device)
+        if q.dim() == 0 or q.shape[-1] != 4:
+            raise ValueError(f"quat_to_euler_xyz: expected (..., 4) quaternions, got {tuple(q.shape)}")
+        flat = q.reshape(-1, 4).contiguous()
+        out = torch.empty(flat.shape[0], 3, device=self.device)
+        self._call("ps_quat_to_euler_xyz", self._ctx, _ptr(flat), _ptr(out), flat.shape[0], self._stream())
+        return out.reshape(*q.shape[:-1], 3)
+
 
 # ---------------------------------------------------------------- helpers
 PLANE_Z = -0.4                      # tasks/*.py: create_plane(z_offset=-0.4)

@@ -9,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "push"
-kern = sys.argv[2] if len(sys.argv) > 2 else "k_step<1, 0, 1>"
+kern = sys.argv[2] if len(sys.argv) > 2 else "k_step<1, 0, 1, false>"
 sums, counts = collections.defaultdict(float), collections.defaultdict(set)
 for sub in (f"stall_sq_{tag}", f"stall_sqc_{tag}"):
     path = os.path.join(ROOT, "gpurun_out", sub, "run_counter_collection.csv")

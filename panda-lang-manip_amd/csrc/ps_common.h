@@ -287,20 +287,14 @@ PS_D float dpp_f(float x) {
 // state row; blocks are observed to go round-robin over the 8 XCDs (b and
 // b + 8 share one, MI355X_MICROARCH.md), so those waves sat on different XCDs
 // and each XCD's L2 fetched the line again: FETCH 934 B per env-step at 8 lanes
-// and 1 424 B at 16 against 210 and 161 on one lane (profiles/r06m_*).  Two
-// bijective remaps put a line's waves on one XCD: the whole range (the blocks
-// of one XCD take consecutive envs) and tiles (runs of T consecutive waves on
-// one XCD, the runs dealt over the XCDs in turn).  Timed on the same sources
-// (profiles/r06o_ab.log, r06p_ab.log, three rotations each), the whole-range
-// remap costs 0.9 % at 8 lanes and nothing at 16, the tiles nothing at 8 and
-// 1.2 % at 16: the product takes tiles at 8 lanes and the whole range at 16.
-// Speed only: an env's results do not depend on the wave it runs in (the
-// group tests and scripts/compare_libs.py, bit for bit).
-// PS_XCD_REMAP (scripts/build_variants.py): 0 none, 1 the product's choice,
-// 2 the whole range at 8 and 16 lanes, 3 tiles at 8 and 16 lanes.
-#ifndef PS_XCD_REMAP
-#define PS_XCD_REMAP 1
-#endif
+// and 1 424 B at 16 against 210 and 161 on one lane.  Two bijective remaps put
+// a line's waves on one XCD: tiles (runs of T consecutive waves on one XCD, the
+// runs dealt over the XCDs in turn), taken at 8 lanes, and the whole range (the
+// blocks of one XCD take consecutive envs), taken at 16: each is the one that
+// costs nothing at its width (the A/B of both at both widths: DESIGN.md §12.13).
+// The one-lane kernels keep the physical order.  Speed only: an env's results
+// do not depend on the wave it runs in (the group tests and
+// scripts/compare_libs.py, bit for bit).
 // runs of T consecutive logical blocks on one XCD, the runs dealt over the
 // XCDs in turn; the blocks past the last whole run of 8 T keep their order
 template <uint32_t T>
@@ -318,10 +312,9 @@ PS_D uint32_t xcd_whole(uint32_t b, uint32_t n) {
 template <int G>
 PS_D uint32_t step_block() {
     const uint32_t b = blockIdx.x;
-    constexpr bool TILES = (PS_XCD_REMAP == 1 && G == 8) || PS_XCD_REMAP == 3;
-    if constexpr (G == 1 || PS_XCD_REMAP == 0) {
+    if constexpr (G == 1) {
         return b;
-    } else if constexpr (TILES) {
+    } else if constexpr (G == 8) {
         return xcd_tiles<G / 2>(b, gridDim.x);
     } else {
         return xcd_whole(b, gridDim.x);
@@ -332,13 +325,9 @@ PS_D uint32_t step_block() {
 // summand is a product, and contracting `J v + dpp(J v)` into fma(J, v, dpp)
 // rounds this lane's term differently from the partner's copy of it, so the
 // lanes of a group would end with different bits (and could leave the PGS loop
-// on different iterations).  PS_EXPERIMENT_GROUP_SUM_CONTRACT (a diagnostic
-// build of scripts/build_variants.py, never the product) leaves contraction on,
-// to show what it does to the group kernels.
+// on different iterations).
 PS_D float group16_sum(float x) {
-#ifndef PS_EXPERIMENT_GROUP_SUM_CONTRACT
 #pragma clang fp contract(off)
-#endif
     x += dpp_f<0x128>(x);  // row_ror:8
     x += dpp_f<0x141>(x);  // row_half_mirror
     x += dpp_f<0xB1>(x);   // quad_perm [1,0,3,2]
@@ -357,9 +346,7 @@ PS_D float group16_bcast(float x) {
 // the same over groups of 8 lanes: half_mirror pairs lane i with 7 - i, then
 // the quad swaps (every lane of the group ends with the same bits)
 PS_D float group8_sum(float x) {
-#ifndef PS_EXPERIMENT_GROUP_SUM_CONTRACT
 #pragma clang fp contract(off)
-#endif
     x += dpp_f<0x141>(x);  // row_half_mirror
     x += dpp_f<0xB1>(x);   // quad_perm [1,0,3,2]
     x += dpp_f<0x4E>(x);   // quad_perm [2,3,0,1]
@@ -374,19 +361,6 @@ PS_D float group8_bcast(float x) {
     static_assert(K >= 0 && K < 8, "lane of the group");
     const float lo = dpp_f<0x150 + K>(x), hi = dpp_f<0x158 + K>(x);
     return (__lane_id() & 8u) ? hi : lo;
-}
-
-// groups of 2 lanes (PS_EXPERIMENT_G2, DESIGN.md §12.13: two lanes per env):
-// the pair's other lane by quad_perm [1,0,3,2], the same bits in both lanes
-PS_D float group2_sum(float x) {
-#pragma clang fp contract(off)
-    return x + dpp_f<0xB1>(x);
-}
-// lane K of this lane's pair: quad_perm [K, K, K + 2, K + 2]
-template <int K>
-PS_D float group2_bcast(float x) {
-    static_assert(K == 0 || K == 1, "lane of the pair");
-    return dpp_f<K == 0 ? 0xA0 : 0xF5>(x);
 }
 
 // compile-time loop

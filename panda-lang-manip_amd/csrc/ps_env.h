@@ -95,11 +95,6 @@ uint32_t *ps_iter_dump_buffer();
 float *ps_row_dump_buffer();
 #endif
 
-// minimum waves per SIMD the step kernels are register-allocated for
-#ifndef PS_STEP_MIN_WAVES
-#define PS_STEP_MIN_WAVES 1
-#endif
-
 namespace {
 
 
@@ -192,6 +187,20 @@ struct KParams {
     float *dbg;  // row dump (ps_row_dump_buffer)
 #endif
 };
+
+// Stack: env i's views of the global stash (ensure_stash): the stash rows
+// env-minor, then its pair and gripper rows env-major, then the shared zero block
+PS_D void bind_stack(MJStore &lds, const KParams &P, int64_t i) {
+    const int64_t stride = P.s.stride;
+    lds.gst = P.gstash;
+    lds.gst_stride = stride;
+    lds.goff = StateView::off(i, 4);
+    lds.gpair = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_PAIR_OFFSET * stride +
+                                                             i * (NP * PAIR_FLOATS));
+    lds.ggrip = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_GRIP_OFFSET * stride +
+                                                             i * GRIP_FLOATS);
+    lds.gzero = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_FLOATS * stride);
+}
 
 inline Scene scene_of(const ps_config &c) {
     Scene s;
@@ -312,9 +321,10 @@ PS_D void run_substeps(const KParams &P, int64_t i, int n, float q[9], float qd[
             load_motors(P.s, ii, m);
         }
 #ifdef PS_DEBUG_ROW_DUMP
-        float *dump = (P.dbg && st < 2 && ((uint64_t)blockIdx.x * 64 + __lane_id()) < PS_DUMP_LANES)
-                          ? P.dbg + (((uint64_t)blockIdx.x * 64 + __lane_id()) * 2 + st) * PS_DUMP_ROWS
-                          : nullptr;
+        // by logical block (step_block: the group kernels' XCD remap), so
+        // dump lane l holds env l / G as scripts/row_dump.py reads it
+        const uint64_t dl = (uint64_t)step_block<G>() * 64 + __lane_id();
+        float *dump = (P.dbg && st < 2 && dl < PS_DUMP_LANES) ? P.dbg + (dl * 2 + st) * PS_DUMP_ROWS : nullptr;
 #endif
         substep<NOBJ, SHAPE, STD_MOTORS, G>(P.sc, q, qd, m, bd, lds, wc PS_PROF_ARG PS_DUMP_ARG);
     }
@@ -620,21 +630,18 @@ inline KParams params_of(ps_ctx *c, void *state) {
 // Stack's global stash (the LDS it would use holds its ground rows): one
 // allocation on the first step of a two-object context, never per step
 inline int ensure_stash(ps_ctx *c, hipStream_t st) {
-#ifdef PS_EXPERIMENT_TWO_WAVES
-    const int64_t floats = c->cfg.n_objects == 2 ? GSTASH_FLOATS : GX_FLOATS;
-#else
-    if (c->cfg.n_objects != 2) return PS_OK;
-    const int64_t floats = GSTASH_FLOATS;
-#endif
-    if (c->gstash) return PS_OK;
-    const size_t bytes = sizeof(float) * (floats * c->lay.stride + GSTASH_ZERO_FLOATS);
-    if (hipMalloc((void **)&c->gstash, bytes) != hipSuccess) {
-        c->gstash = nullptr;
+    if (c->cfg.n_objects != 2 || c->gstash) return PS_OK;
+    const size_t bytes = sizeof(float) * ((int64_t)GSTASH_FLOATS * c->lay.stride + GSTASH_ZERO_FLOATS);
+    float *buf = nullptr;
+    if (hipMalloc((void **)&buf, bytes) != hipSuccess) return PS_ERR_HIP;
+    // all-zero (the solver's zero block after the stash, GSTASH_ZERO_FLOATS),
+    // on the stream the steps run on; the context takes the buffer only once
+    // the memset is enqueued, so no later step can find it unzeroed
+    if (hipMemsetAsync(buf, 0, bytes, st) != hipSuccess) {
+        (void)hipFree(buf);
         return PS_ERR_HIP;
     }
-    // all-zero (the solver's zero block after the stash, GSTASH_ZERO_FLOATS),
-    // on the stream the steps run on
-    if (hipMemsetAsync(c->gstash, 0, bytes, st) != hipSuccess) return PS_ERR_HIP;
+    c->gstash = buf;
     return PS_OK;
 }
 
@@ -657,9 +664,9 @@ inline bool scene_matches_task(const ps_config &c) {
 // i's orientation from orn [B, 4] (every lane of a group reads the same four
 // floats, as it does the action); ps_step's kernels never read orn.
 template <int TASK, int CONTROL, int G = 1, bool ORI = false>
-__global__ __launch_bounds__(kBlock, PS_STEP_MIN_WAVES) void k_step(KParams P, const float *actions, float *obs, float *ag, float *dg,
-                                                 float *reward, uint8_t *terminated, uint8_t *truncated,
-                                                 float *final_obs, float *final_ag, const float *orn) {
+__global__ __launch_bounds__(kBlock, 1) void k_step(KParams P, const float *actions, float *obs, float *ag, float *dg,
+                                                    float *reward, uint8_t *terminated, uint8_t *truncated,
+                                                    float *final_obs, float *final_ag, const float *orn) {
     static_assert(!ORI || CONTROL == PS_CONTROL_EE, "a target orientation exists with ee control only");
     using T = TaskTraits<TASK>;
     const int64_t gi = ((int64_t)step_block<G>() * blockDim.x + threadIdx.x) / G;
@@ -699,22 +706,7 @@ __global__ __launch_bounds__(kBlock, PS_STEP_MIN_WAVES) void k_step(KParams P, c
     __shared__ float smem[lds_floats<T::NOBJ>() * NCOL + (SHARED ? CW_OUT_FLOATS * kBlock : 0)];
     MJStore lds{(lds_float *)(smem + (SHARED ? threadIdx.x / G : threadIdx.x)), NCOL};
     lds.cwo = SHARED ? (lds_float *)(smem + lds_floats<T::NOBJ>() * NCOL + threadIdx.x) : lds.base + CW_OUT * kBlock;
-    if constexpr (T::NOBJ == 2) {
-        lds.gst = P.gstash;
-        lds.gst_stride = s.stride;
-        lds.goff = StateView::off(i, 4);
-        lds.gpair = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_PAIR_OFFSET * s.stride +
-                                                                 i * (NP * PAIR_FLOATS));
-        lds.ggrip = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_GRIP_OFFSET * s.stride +
-                                                                 i * GRIP_FLOATS);
-        lds.gzero = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_FLOATS * s.stride);
-    }
-#ifdef PS_EXPERIMENT_TWO_WAVES
-    if constexpr (T::NOBJ < 2) {
-        lds.gx = (__attribute__((address_space(1))) float *)P.gstash;
-        lds.gxl = (uint32_t)(((i >> 6) * (GX_FLOATS * 64) + (i & 63)) * 4);
-    }
-#endif
+    if constexpr (T::NOBJ == 2) bind_stack(lds, P, i);
     run_substeps<T::NOBJ, T::SHAPE, true, G>(P, i, PM_SUBSTEPS, q, qd, bd, lds, live, tgt PS_PROF_ARG);
     double g[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -811,22 +803,7 @@ __global__ __launch_bounds__(kBlock) void k_sim_step(KParams P, int n_substeps) 
     __shared__ float smem[lds_floats<NOBJ>() * kBlock];
     MJStore lds{(lds_float *)(smem + threadIdx.x), kBlock};
     lds.cwo = lds.base + CW_OUT * kBlock;
-    if constexpr (NOBJ == 2) {
-        lds.gst = P.gstash;
-        lds.gst_stride = s.stride;
-        lds.goff = StateView::off(i, 4);
-        lds.gpair = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_PAIR_OFFSET * s.stride +
-                                                                 i * (NP * PAIR_FLOATS));
-        lds.ggrip = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_GRIP_OFFSET * s.stride +
-                                                                 i * GRIP_FLOATS);
-        lds.gzero = (__attribute__((address_space(1))) float *)(P.gstash + (int64_t)GSTASH_FLOATS * s.stride);
-    }
-#ifdef PS_EXPERIMENT_TWO_WAVES
-    if constexpr (NOBJ < 2) {
-        lds.gx = (__attribute__((address_space(1))) float *)P.gstash;
-        lds.gxl = (uint32_t)(((i >> 6) * (GX_FLOATS * 64) + (i & 63)) * 4);
-    }
-#endif
+    if constexpr (NOBJ == 2) bind_stack(lds, P, i);
 #ifdef PS_PROFILE_PHASES
     PhaseTimer pt;
     pt.last = (uint32_t)__builtin_amdgcn_s_memtime();

@@ -693,12 +693,8 @@ constexpr int GRIP_FLOATS = GRIP_MJ_SLOTS * 9;
 constexpr int GSTASH_FLOATS = GSTASH_GRIP_OFFSET + GRIP_FLOATS;
 template <int NOBJ>
 constexpr int lds_floats() {
-#ifdef PS_EXPERIMENT_TWO_WAVES
-    if (NOBJ < 2) return 61;
-#endif
     return NOBJ == 2 ? LDS_FLOATS_STACK : LDS_FLOATS;
 }
-constexpr int GX_FLOATS = LDS_STASH_OFFSET + LDS_STASH_FLOATS;  // PS_EXPERIMENT_TWO_WAVES
 
 // object-ground contact: object-only rows; normal +z, friction dirs of
 // planeSpace(+z) = (0,-1,0), (1,0,0).  The cylinder's I^-1 (r x dir) is rebuilt
@@ -734,32 +730,9 @@ struct MJStore {
     // in this lane's column (base + CW_OUT rows) unless the env's column is
     // shared by its group's lanes (shared_lds<G>)
     lds_float *cwo = nullptr;
-#ifdef PS_EXPERIMENT_TWO_WAVES
-    // Experiment: the one-object kernels at
-    // two waves per SIMD.  The M^-1 J^T rows, the candidate records and the
-    // stash (floats [0, 148) of the LDS column) move to a wave-tiled global
-    // buffer (as Stack's stash: element k of env i at ((i / 64) * 148 + k) * 64
-    // + i % 64); LDS keeps the work lists' 51 floats and the contact cache, 61
-    // floats per lane, and the kernel is register-allocated for two waves.
-    __attribute__((address_space(1))) float *gx = nullptr;
-    uint32_t gxl = 0;
-    PS_D float &gxr(int k) const {
-        __attribute__((address_space(1))) float *page = gx + (k / 16) * 1024;
-        asm("" : "+s"(page));
-        return *(float *)((__attribute__((address_space(1))) char *)page + gxl + (k % 16) * 256);
-    }
-    // an index that varies by lane (a candidate slot): the whole address per lane
-    PS_D float &gxd(int k) const {
-        return *(float *)((__attribute__((address_space(1))) char *)gx + gxl + (uint32_t)k * 256u);
-    }
-    PS_D float &at(int slot, int row, int k) const { return gxr((slot * 3 + row) * 9 + k); }
-    PS_D lds_float &cache(int k) const { return base[(51 + k) * stride]; }
-    PS_D float &stash(int k) const { return gxr(LDS_STASH_OFFSET + k); }
-#else
     PS_D lds_float &at(int slot, int row, int k) const { return base[((slot * 3 + row) * 9 + k) * stride]; }
     PS_D lds_float &cache(int k) const { return base[(LDS_CACHE_OFFSET + k) * stride]; }
     PS_D lds_float &stash(int k) const { return base[(LDS_STASH_OFFSET + k) * stride]; }
-#endif
     // Stack: the stash in global memory ([GSTASH_PAIR_OFFSET][stride] floats, this env's column)
     // (wave-uniform base and stride, the lane's byte offset: global_* v_off, s[base])
     float *gst = nullptr;
@@ -796,9 +769,6 @@ struct MJStore {
     PS_D MJStore opaque() const {
         MJStore r = *this;
         asm volatile("" : "+v"(r.base));
-#ifdef PS_EXPERIMENT_TWO_WAVES
-        asm volatile("" : "+v"(r.gxl));
-#endif
         asm volatile("" : "+v"(r.goff));
         asm volatile("" : "+v"(r.gpair));
         asm volatile("" : "+v"(r.ggrip));
@@ -1599,14 +1569,12 @@ PS_D float cone_scale(float m2, float lim) {
 template <int G>
 PS_D float group_sum(float x) {
     if constexpr (G == 16) return group16_sum(x);
-    else if constexpr (G == 8) return group8_sum(x);
-    else return group2_sum(x);
+    else return group8_sum(x);
 }
 template <int G, int K>
 PS_D float group_bcast(float x) {
     if constexpr (G == 16) return group16_bcast<K>(x);
-    else if constexpr (G == 8) return group8_bcast<K>(x);
-    else return group2_bcast<K>(x);
+    else return group8_bcast<K>(x);
 }
 template <int NOBJ, int SHAPE, bool STD_MOTORS, int G>
 PS_D void group_pgs(const Motors &mt, const float Mi[45], const MJStore &lds, unsigned gate_lim, unsigned lim_up,
@@ -1614,8 +1582,7 @@ PS_D void group_pgs(const Motors &mt, const float Mi[45], const MJStore &lds, un
                     const float lim_rhs[9], float lim_lam[9], const float mot_rhs[9], float mot_lam[9],
                     GroundContact gc[NG], RobotContact rc[NR], const BodyDyn<SHAPE> &od, float gmu, float dv[9],
                     V3 &dw, V3 &dvl PS_PROF_COUNT_PARAM PS_DUMP_PARAM) {
-    // (G = 2: the PS_EXPERIMENT_G2 kernels, eight DoF slots per lane)
-    static_assert((G == 16 || G == 8 || G == 2) && NOBJ <= 1, "groups of 16, 8 or 2 lanes hold 9 robot + 6 object DoFs");
+    static_assert((G == 16 || G == 8) && NOBJ <= 1, "groups of 16 or 8 lanes hold 9 robot + 6 object DoFs");
 #ifdef PS_DEBUG_ROW_DUMP
     int dk = 0;
     auto rec = [&](float x) {
@@ -1633,7 +1600,10 @@ PS_D void group_pgs(const Motors &mt, const float Mi[45], const MJStore &lds, un
 #pragma unroll
         for (int j = 0; j < 3; j++) { rec(rc[c].rhs[j]); rec(rc[c].dinv[j]); rec(rc[c].lam[j]); }
     rec(__builtin_bit_cast(float, gate_lim | (gate_gnd << 9) | (gate_robot << 13)));
-    bool dump_on = dump != nullptr;
+    // wave-uniform (rec tests each lane's pointer): a per-lane flag put the
+    // loop's scalar gates (regate) inside divergent branches, which this
+    // compiler refuses ("illegal VGPR to SGPR copy")
+    bool dump_on = __builtin_amdgcn_ballot_w64(dump != nullptr) != 0;
 #define PS_REC(x) do { if (dump_on) rec(x); } while (0)
 #else
 #define PS_REC(x) do {} while (0)
@@ -1923,24 +1893,12 @@ struct RobotCand {
         const float v[FLOATS] = {pA.x, pA.y, pA.z, pB.x, pB.y, pB.z, n.x, n.y, n.z, dist, mu,
                                  (float)link, (float)obj, (float)id};
 #pragma unroll
-        for (int k = 0; k < FLOATS; k++) {
-#ifdef PS_EXPERIMENT_TWO_WAVES
-            L.gxd(OFFSET + s * FLOATS + k) = v[k];
-#else
-            L.base[(OFFSET + s * FLOATS + k) * L.stride] = v[k];
-#endif
-        }
+        for (int k = 0; k < FLOATS; k++) L.base[(OFFSET + s * FLOATS + k) * L.stride] = v[k];
     }
     PS_D static RobotCand load(const MJStore &L, int s) {
         float v[FLOATS];
 #pragma unroll
-        for (int k = 0; k < FLOATS; k++) {
-#ifdef PS_EXPERIMENT_TWO_WAVES
-            v[k] = L.gxd(OFFSET + s * FLOATS + k);
-#else
-            v[k] = L.base[(OFFSET + s * FLOATS + k) * L.stride];
-#endif
-        }
+        for (int k = 0; k < FLOATS; k++) v[k] = L.base[(OFFSET + s * FLOATS + k) * L.stride];
         return RobotCand{mk(v[0], v[1], v[2]), mk(v[3], v[4], v[5]), mk(v[6], v[7], v[8]), v[9], v[10],
                          (int)v[11], (int)v[12], (int)v[13]};
     }
@@ -2655,13 +2613,7 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
 #pragma unroll
     for (int b = 0; b < NB; b++) gate_ground[b] = wave_bits([&](int c) { return c < ng[b]; }, NG);
     unsigned gate_pair = wave_bits([&](int c) { return c < np; }, NP);
-#ifdef PS_EXPERIMENT_NO_PAIR_ROWS
-    gate_pair = 0u;  // timing experiment only (wrong physics): Stack's solve without its box-box rows
-#endif
     unsigned gate_robot = wave_bits([&](int c) { return c < nr; }, NR);
-#ifdef PS_EXPERIMENT_NO_ROBOT_ROWS
-    gate_robot = 0u;  // timing experiment only (wrong physics): the solve without the gripper rows
-#endif
 
 #ifdef PS_PROFILE_PHASES
     int prof_it = 0;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""FETCH_SIZE / WRITE_SIZE of the step kernel against the batch size (the
-passes of scripts/passes/gpu_r06m.sh): per-launch bytes (FETCH x 2, the gfx950
+"""FETCH_SIZE / WRITE_SIZE of the step kernel against the batch size (round 6's
+counter passes, profiles/r06m_*): per-launch bytes (FETCH x 2, the gfx950
 correction of summarize_profiles.py) for each run directory
 gpurun_out/<prefix>_<tag>_{fetch,write}/ (prefix: argv[1], default fvb), and a least-squares line bytes = a + b B
 per kernel, to split the per-launch traffic into a part that grows with the

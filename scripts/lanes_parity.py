@@ -2,9 +2,10 @@
 """Teacher-forced parity of one step-kernel variant (test_gpu_parity.py's
 test_env_step_parity_teacher_forced workload: 64 envs, seeds 12345 + i, 10
 steps of default_rng(7) actions, each GPU step judged against one oracle step
-from the same state by tests/parity_judge.judge), for a library and a lanes-per-
-env value the test suite does not parametrise -- the round-6 G = 2 experiment
-(PANDASIM_LIB=scripts/bin/variants/lib_g2.so).
+from the same state by tests/parity_judge.judge), for another library than
+the product (PANDASIM_LIB: a build of scripts/build_variants.py) at 1, 8 or 16
+lanes per env.  Written for the round-6 two-lanes-per-env experiment, whose
+kernels are no longer in the tree.
 
   PANDASIM_LIB=... python scripts/lanes_parity.py LANES TASK CONTROL
 """

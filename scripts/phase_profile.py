@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "panda-lang-manip_amd"))
-# (PANDASIM_PROF_LIB: another diagnostic build, e.g. an experiment of scripts/build_variants.py)
+# (PANDASIM_PROF_LIB: another -DPS_PROFILE_PHASES build, e.g. one with other compiler flags)
 os.environ["PANDASIM_LIB"] = os.environ.get("PANDASIM_PROF_LIB") or os.path.join(
     ROOT, "panda-lang-manip_amd", "pandasim", "libpandasim_prof.so")
 

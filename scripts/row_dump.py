@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """The group solver's row dump (-DPS_DEBUG_ROW_DUMP builds: scripts/build_variants.py
-dump, groups_o3_dump) of one fused step from a reset, for each library given,
-and the first record where the libraries differ per lane (the -O3 group-kernel
-investigation).  Records per lane and substep (0, 1): the
+dump, or that build of another checkout or with other flags) of one fused step
+from a reset, for each library given, and the first record where the libraries
+differ per lane (the -O3 group-kernel investigation).  The
+dump is indexed by logical block (ps_common.h step_block), so dump lane l
+belongs to env l // LANES.  Records per lane and substep (0, 1): the
 solver inputs (motor rhs, 1/den, limit rhs per DoF; ground rows' rhs and 1/den;
 gripper rows' rhs, 1/den, warm start; the gates), then each row's impulse
 change in the first iteration pair, then that pair's residual.

@@ -662,6 +662,21 @@ def test_ragged_batch_parity(ps, B, lanes):
 GROUP_TASKS = [(t, c) for t, c in TASKS if t != "stack"]
 
 
+def test_lanes_per_env_accepts_0_1_8_16_only(ps):
+    """ps_set_lanes_per_env takes 0 (the library's choice), 1, 8 and 16; any
+    other value is PS_ERR_ARG and leaves the context's choice as it was."""
+    from pandasim import _lib as L
+
+    env = make_env(ps, "reach", "ee", 8, lanes=8)
+    lib, ctx = env.sim._lib, env.sim._ctx
+    for lanes in (2, 4, 32):
+        assert L.ERRORS[lib.ps_set_lanes_per_env(ctx, lanes)] == "PS_ERR_ARG", lanes
+        assert lib.ps_step_lanes(ctx) == 8, lanes
+    for lanes, used in ((1, 1), (16, 16), (8, 8), (0, 16)):  # 0: 16 lanes for a batch this small
+        assert lib.ps_set_lanes_per_env(ctx, lanes) == 0, lanes
+        assert lib.ps_step_lanes(ctx) == used, lanes
+
+
 @pytest.mark.parametrize("B", [64, 1000])
 @pytest.mark.parametrize("task,control", GROUP_TASKS)
 def test_group_kernels_match_one_lane(ps, task, control, B):

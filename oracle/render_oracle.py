@@ -17,6 +17,10 @@ for libpandasim's ps_camera / ps_render / ps_deproject_*.
               kernels draw (plane, table, objects, the arm's capsule proxies and
               gripper spheres), for small images: the GPU depth buffer is
               checked against it.
+* raycast_image(): the same scene as an fp64 image after DESIGN.md §11's
+              shading specification (role, primitive, face, normal, ghost
+              flags, colour before and after quantisation) with a per-pixel
+              "stable" mask: the GPU colour buffer is checked against it.
 """
 from __future__ import annotations
 
@@ -252,3 +256,164 @@ def raycast_depth(cfg, env, view, proj, width, height):
     with np.errstate(invalid="ignore", divide="ignore"):
         dep = 0.5 * ((P[2, 2] * (-t) + P[2, 3]) / t) + 0.5
     return np.where(np.isfinite(t), dep, 1.0).reshape(height, width)
+
+
+# ------------------------------------------------------------ image
+# visual roles: the rows of ps_visual.rgba (include/pandasim.h)
+ROLE_PLANE, ROLE_TABLE, ROLE_OBJECT1, ROLE_OBJECT2, ROLE_TARGET1, ROLE_TARGET2, ROLE_ROBOT, ROLE_BACKGROUND = range(8)
+SHAPE_BOX, SHAPE_CYLINDER, VISUAL_SPHERE = 0, 1, 2  # ps_visual.target_shape
+# primitive ids: plane, table, object 1, object 2, the arm's capsules, then the gripper spheres; -1 = nothing
+PRIM_PLANE, PRIM_TABLE, PRIM_OBJECT, PRIM_ARM = 0, 1, 2, 4
+# faces: boxes 2 * axis + (0 for the + side, 1 for the - side) in the box's own frame;
+# cylinders 0 = side, 1 = cap at -z, 2 = cap at +z; everything else -1
+CYL_SIDE, CYL_BOTTOM, CYL_TOP = 0, 1, 2
+
+
+def _unit_quat_mat(q):
+    q = np.asarray(q, np.float64)
+    return _quat_mat(q / np.linalg.norm(q))
+
+
+def _safe(t):
+    return np.where(np.isfinite(t), t, 0.0)
+
+
+def _box_hit(eye, d, c, R, h):
+    """Entry t [N], outward unit normal [N, 3] and face index [N] of the box:
+    the face is read off the hit point (the coordinate that sits on its slab)."""
+    h = np.asarray(h, np.float64)
+    t = _box(eye, d, c, R, h)
+    p = (eye - c) @ R + _safe(t)[:, None] * (d @ R)
+    axis = np.argmax(np.abs(p) / h, axis=1)
+    sign = np.where(np.take_along_axis(p, axis[:, None], 1)[:, 0] >= 0, 1.0, -1.0)
+    n = R.T[axis] * sign[:, None]
+    return t, n, 2 * axis + (sign < 0)
+
+
+def _cylinder_hit(eye, d, c, R, r, hh):
+    lo = (eye - c) @ R
+    ld = d @ R
+    a = ld[:, 0] ** 2 + ld[:, 1] ** 2
+    b = lo[0] * ld[:, 0] + lo[1] * ld[:, 1]
+    disc = b * b - a * (lo[0] ** 2 + lo[1] ** 2 - r * r)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ts = (-b - np.sqrt(disc)) / a
+        ts = np.where((disc >= 0) & (np.abs(lo[2] + ts * ld[:, 2]) <= hh), ts, np.inf)
+        tcap = []
+        for zc in (-hh, hh):
+            tc = (zc - lo[2]) / ld[:, 2]
+            x, y = lo[0] + tc * ld[:, 0], lo[1] + tc * ld[:, 1]
+            tcap.append(np.where(x * x + y * y <= r * r, tc, np.inf))
+    # all three are points of the (convex) body's surface on the ray: the nearest is the entry
+    tt = np.stack([ts, tcap[0], tcap[1]], 1)
+    face = np.argmin(tt, axis=1)
+    t = tt[np.arange(len(tt)), face]
+    p = lo + _safe(t)[:, None] * ld
+    radial = np.stack([p[:, 0], p[:, 1], np.zeros(len(p))], 1) / r
+    nl = np.where((face == CYL_SIDE)[:, None], radial, np.array([0.0, 0.0, 1.0]) * np.where(face == CYL_TOP, 1.0, -1.0)[:, None])
+    return t, nl @ R.T, face
+
+
+def _sphere_hit(eye, d, c, r):
+    t = _sphere(eye, d, c, r)
+    return t, (eye + _safe(t)[:, None] * d - c) / r, np.full(len(d), -1)
+
+
+def _capsule_hit(eye, d, pa, pb, r):
+    t = _capsule(eye, d, pa, pb, r)
+    p = eye + _safe(t)[:, None] * d - pa
+    ba = pb - pa
+    s = np.clip(p @ ba / (ba @ ba), 0.0, 1.0)
+    return t, (p - s[:, None] * ba) / r, np.full(len(d), -1)
+
+
+def light_vector(view):
+    """The key light of DESIGN.md §11: normalize(0.6 u - 0.3 f + (0, 0, 0.7)), u and f the view matrix's up and forward."""
+    V = np.asarray(view, np.float64).reshape(4, 4, order="F")
+    l = 0.6 * V[1, :3] + 0.3 * V[2, :3] + np.array([0.0, 0.0, 0.7])  # f = -V[2, :3]
+    return l / np.linalg.norm(l)
+
+
+def quantise(c):
+    """u8 of a colour in [0, 1]: floor(255 c + 0.5), clipped."""
+    return np.clip(np.floor(255.0 * np.asarray(c, np.float64) + 0.5), 0, 255).astype(np.uint8)
+
+
+def stable_mask(*keys):
+    """Pixels [h, w] on which every key image equals itself on all neighbours that exist."""
+    ok = np.ones(keys[0].shape[:2], bool)
+    h, w = ok.shape
+    for k in keys:
+        k = k.reshape(h, w, -1)
+        pad = np.pad(k, ((1, 1), (1, 1), (0, 0)), mode="edge")  # past the border: an existing pixel again
+        for di in (0, 1, 2):
+            for dj in (0, 1, 2):
+                ok &= np.all(pad[di:di + h, dj:dj + w] == k, axis=2)
+    return ok
+
+
+def raycast_image(cfg, env, view, proj, width, height, visual, targets):
+    """The camera image of one env in fp64 after DESIGN.md §11.
+
+    visual: anything with ps_visual's fields (rgba [8][4], target_shape [2],
+    target_half [2][3]); targets: [2, 7] ghost poses (pos, quat xyzw) or None.
+    -> dict of [h, w(, k)] arrays: t, t2 (nearest and second-nearest opaque
+    entry along the view axis, inf where none), role, prim, face, normal,
+    ghost (entry of ghost g in [near, t)), ghost_t (its entry, inf where the
+    ray misses it), color (fp64), rgb (u8), depth (window depth) and stable."""
+    eye, d, P, near, far = _rays(view, proj, width, height)
+    N = d.shape[0]
+    hits = []  # (role, prim, (t, n, face))
+    if cfg.has_plane:
+        hits.append((ROLE_PLANE, PRIM_PLANE, _box_hit(eye, d, np.array([0, 0, PLANE_TOP - 0.01]), np.eye(3),
+                                                      (3.0, 3.0, 0.01))))
+    if cfg.has_table:
+        hits.append((ROLE_TABLE, PRIM_TABLE, _box_hit(eye, d, np.array([cfg.table_cx, 0.0, TABLE_TOP - 0.2]),
+                                                      np.eye(3), (cfg.table_hx, cfg.table_hy, 0.2))))
+    half = np.array([cfg.object_half[k] for k in range(3)], np.float64)
+    for ob in range(cfg.n_objects):
+        c, R = np.array(env.obj[ob].pos[:]), _unit_quat_mat(env.obj[ob].quat[:])
+        hit = _cylinder_hit(eye, d, c, R, half[0], half[2]) if cfg.object_shape == 1 else _box_hit(eye, d, c, R, half)
+        hits.append((ROLE_OBJECT1 + ob, PRIM_OBJECT + ob, hit))
+    caps, sph = scene_primitives(cfg, env)
+    for k, (a, b, r) in enumerate(caps):
+        hits.append((ROLE_ROBOT, PRIM_ARM + k, _capsule_hit(eye, d, a, b, r)))
+    for k, (c, r) in enumerate(sph):
+        hits.append((ROLE_ROBOT, PRIM_ARM + len(caps) + k, _sphere_hit(eye, d, c, r)))
+    # a primitive entered before the near plane (or past the far plane) is not drawn on that ray
+    T = np.stack([np.where((h[0] >= near) & (h[0] < far), h[0], np.inf) for _, _, h in hits], 1)
+    order = np.argsort(T, axis=1, kind="stable")
+    first, rows = order[:, 0], np.arange(N)
+    t = T[rows, first]
+    t2 = T[rows, order[:, 1]] if T.shape[1] > 1 else np.full(N, np.inf)
+    hit = np.isfinite(t)
+    role = np.where(hit, np.array([h[0] for h in hits])[first], ROLE_BACKGROUND)
+    prim = np.where(hit, np.array([h[1] for h in hits])[first], -1)
+    normal = np.stack([h[2][1] for h in hits], 1)[rows, first]
+    normal = np.where(hit[:, None], normal, 0.0)
+    face = np.where(hit, np.stack([h[2][2] for h in hits], 1)[rows, first], -1)
+    rgba = np.array([[visual.rgba[r][k] for k in range(4)] for r in range(8)], np.float64)
+    shade = np.where(hit, 0.35 + 0.65 * np.abs(normal @ light_vector(view)), 1.0)
+    color = rgba[role, :3] * shade[:, None]
+    ghost, ghost_t = np.zeros((N, 2), bool), np.full((N, 2), np.inf)
+    for g in range(2):
+        shape = int(visual.target_shape[g])
+        if shape < 0 or targets is None:
+            continue
+        pose = np.asarray(targets, np.float64)[g]
+        gh = [float(visual.target_half[g][k]) for k in range(3)]
+        R = _unit_quat_mat(pose[3:])
+        tg = (_cylinder_hit(eye, d, pose[:3], R, gh[0], gh[2]) if shape == SHAPE_CYLINDER
+              else _sphere_hit(eye, d, pose[:3], gh[0]) if shape == VISUAL_SPHERE
+              else _box_hit(eye, d, pose[:3], R, gh))[0]
+        ghost_t[:, g] = tg
+        ghost[:, g] = (tg >= near) & (tg < np.where(hit, t, far))
+        al = rgba[ROLE_TARGET1 + g, 3]
+        color = np.where(ghost[:, g:g + 1], al * rgba[ROLE_TARGET1 + g, :3] + (1.0 - al) * color, color)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dep = np.where(hit, 0.5 * ((P[2, 2] * (-t) + P[2, 3]) / t) + 0.5, 1.0)
+    im = lambda a: a.reshape(height, width, *a.shape[1:])
+    out = {"t": im(t), "t2": im(t2), "role": im(role), "prim": im(prim), "face": im(face), "normal": im(normal),
+           "ghost": im(ghost), "ghost_t": im(ghost_t), "color": im(color), "rgb": im(quantise(color)), "depth": im(dep)}
+    out["stable"] = stable_mask(out["role"], out["prim"], out["face"], out["ghost"])
+    return out

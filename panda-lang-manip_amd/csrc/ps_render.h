@@ -72,7 +72,11 @@ PS_D bool ray_box(V3 o, V3 d, V3 c, const M3 &R, V3 h, float tmin, Hit &hit) {
 // upright (local z) capped cylinder of radius r and half height hh
 PS_D bool ray_cylinder(V3 o, V3 d, V3 c, const M3 &R, float r, float hh, float tmin, Hit &hit) {
     V3 lo = tmul(R, o - c), ld = tmul(R, d);
-    bool got = false;
+    // the entry is the nearest of the side's first root and the two caps; like the
+    // other shapes, a cylinder entered before tmin is not drawn on this ray (testing
+    // tmin per surface would draw the far cap's inside where the near plane cuts it)
+    float te = 3.0e38f;
+    V3 nl = mk(0, 0, 1);  // normal in the cylinder's frame
     float a = ld.x * ld.x + ld.y * ld.y;
     if (a > 1e-20f) {
         float b = lo.x * ld.x + lo.y * ld.y, cc = lo.x * lo.x + lo.y * lo.y - r * r;
@@ -80,11 +84,10 @@ PS_D bool ray_cylinder(V3 o, V3 d, V3 c, const M3 &R, float r, float hh, float t
         if (disc >= 0.0f) {
             float t = (-b - sqrtf(disc)) * frcp(a);
             float z = lo.z + t * ld.z;
-            if (t >= tmin && t < hit.t && fabsf(z) <= hh) {
-                hit.t = t;
+            if (fabsf(z) <= hh) {
+                te = t;
                 float ir = frcp(r);
-                hit.n = mul(R, mk((lo.x + t * ld.x) * ir, (lo.y + t * ld.y) * ir, 0.0f));
-                got = true;
+                nl = mk((lo.x + t * ld.x) * ir, (lo.y + t * ld.y) * ir, 0.0f);
             }
         }
     }
@@ -94,14 +97,16 @@ PS_D bool ray_cylinder(V3 o, V3 d, V3 c, const M3 &R, float r, float hh, float t
             float zc = s ? hh : -hh;
             float t = (zc - lo.z) * frcp(ld.z);
             float x = lo.x + t * ld.x, y = lo.y + t * ld.y;
-            if (t >= tmin && t < hit.t && x * x + y * y <= r * r) {
-                hit.t = t;
-                hit.n = col(R, 2) * (s ? 1.0f : -1.0f);
-                got = true;
+            if (t < te && x * x + y * y <= r * r) {
+                te = t;
+                nl = mk(0.0f, 0.0f, s ? 1.0f : -1.0f);
             }
         }
     }
-    return got;
+    if (!(te >= tmin && te < hit.t)) return false;
+    hit.t = te;
+    hit.n = mul(R, nl);
+    return true;
 }
 
 // does the ray meet the sphere (c, r) at some t < tmax?  (culling only)

@@ -242,6 +242,77 @@ int ps_link_state(ps_ctx *ctx, const void *state, int link, float *pos, float *q
 int ps_inverse_kinematics(ps_ctx *ctx, const void *state, int link, const float *pos, const float *orn,
                           float *q_out, void *stream);
 
+/* --- Cartesian motion primitives (panda_cartesian.py:53-145), fused ---
+ *
+ * move / grasp / release of the language-manipulation pipeline's robot, per
+ * env: a plan call fills a plan from the state, ps_motion_run executes its
+ * control steps (Cartesian set_action + PyBullet.step each).  They touch no
+ * goal, generator, TimeLimit counter, observation or reward.
+ *
+ * The plan is a caller-owned device buffer of ps_motion_plan_bytes(num_envs)
+ * bytes, structure-of-arrays with the state's stride (ps_layout.stride):
+ * PS_PLAN_NUM_F64_ROWS rows of `stride` doubles, then PS_PLAN_NUM_I32_ROWS
+ * rows of `stride` int32 (env i at [row*stride + i]).  A zeroed buffer is a
+ * valid plan with nothing to do. */
+enum {
+    PS_PLAN_START = 0,  /* 3 f64: move: ee position when the plan was made */
+    PS_PLAN_DELTA = 3,  /* 3 f64: move: (goal - start) / num_steps */
+    PS_PLAN_WIDTH = 6,  /* 1 f64: action[3]: move: finger width at plan time; grasp 1; release `width` */
+    PS_PLAN_Q0 = 7,     /* 4 f64: ee link quaternion at plan time (x, y, z, w), unit */
+    PS_PLAN_ROTVEC = 11, /* 3 f64: move: rotation vector of R_start^-1 R_goal (angle <= pi) */
+    PS_PLAN_NUM_F64_ROWS = 14
+};
+enum {
+    PS_PLAN_NUM_STEPS = 0, /* control steps of the plan */
+    PS_PLAN_DONE = 1,      /* control steps executed so far */
+    PS_PLAN_BLOCKED = 2,   /* gripper blocked (finger targets 0): set by grasp, cleared by release, kept by move */
+    PS_PLAN_KIND = 3,      /* PS_PLAN_KIND_MOVE or PS_PLAN_KIND_HOLD */
+    PS_PLAN_NUM_I32_ROWS = 4
+};
+enum { PS_PLAN_KIND_MOVE = 0, PS_PLAN_KIND_HOLD = 1 };
+#define PS_PLAN_HOLD_STEPS 30 /* control steps of grasp and release (panda_cartesian.py:127, 142) */
+
+/* Bytes of a plan buffer for num_envs envs (PS_ERR_ARG, negative, for a batch
+ * ps_state_layout rejects). */
+int64_t ps_motion_plan_bytes(int64_t num_envs);
+
+/* Panda.move(goal_pos, goal_euler) up to its loop (panda_cartesian.py:98-114)
+ * for every env with mask[i] != 0 (mask == NULL: all): start = ee position,
+ * start orientation = ee link quaternion, finger_width = q9 + q10, d = |goal -
+ * start|, num_steps = 20 when d < 0.03, else d // 0.015 (+ 1 when d % 0.015 >
+ * 1e-3), delta = (goal - start) / num_steps; fp64 arithmetic on the f32 state.
+ * goal_pos: device [B, 3] f32 world; goal_quat: device [B, 4] f32 (x, y, z, w;
+ * normalised; ps_euler_xyz_to_quat of goal_euler).  The orientation is
+ * interpolated as scipy's Slerp([1, num_steps], [start, goal]) does, along the
+ * shortest arc.  Sets done = 0 and keeps the plan's blocked row (the caller
+ * writes it: the reference's block_gripper).  Envs with mask[i] == 0 get
+ * num_steps = done = 0. */
+int ps_plan_move(ps_ctx *ctx, const void *state, void *plan, const float *goal_pos, const float *goal_quat,
+                 const uint8_t *mask, void *stream);
+
+/* Panda.grasp() (panda_cartesian.py:124-130): blocked := 1 and 30 control
+ * steps of action (0, 0, 0, 1) with the ee link's orientation of that step.
+ * Envs with mask[i] == 0 get num_steps = done = 0 and keep blocked. */
+int ps_plan_grasp(ps_ctx *ctx, const void *state, void *plan, const uint8_t *mask, void *stream);
+
+/* Panda.release(width) (panda_cartesian.py:139-145): blocked := 0 and 30
+ * control steps of action (0, 0, 0, width[i]); width: device [B] f32, NULL = 1. */
+int ps_plan_release(ps_ctx *ctx, const void *state, void *plan, const float *width, const uint8_t *mask,
+                    void *stream);
+
+/* The loops of move / grasp / release (panda_cartesian.py:116-122, 127-130,
+ * 142-145), fused: every env executes min(max_steps, num_steps - done) control
+ * steps -- the step's waypoint and orientation, Cartesian Panda.set_action
+ * (:53-72, 147-176: action clipped to [-1, 1], target = ee position +
+ * action[:3] unscaled, z >= 0, calculateInverseKinematics on link 11, finger
+ * targets 0 when blocked else (width + action[3]) / 2, POSITION_CONTROL as
+ * ps_step), PyBullet.step (20 substeps) -- and advances done.  An env with no
+ * steps left keeps its state bits; an env's result does not depend on how
+ * many steps the other envs run, nor on how the steps are split over calls.
+ * The motor gain rows are written with ps_step's values.  Any context (any
+ * task, either control type).  PS_ERR_ARG: a NULL buffer or max_steps < 1. */
+int ps_motion_run(ps_ctx *ctx, void *state, void *plan, int max_steps, void *stream);
+
 /* --- pieces of the unfused (Robot/Task plugin) path, pandasim/core.py --- */
 
 #define PS_MAX_UNIFORM 8

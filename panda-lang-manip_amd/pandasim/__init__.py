@@ -2,6 +2,7 @@
 
 Host layer over libpandasim.so (HIP, gfx950).  See DESIGN.md.
 """
+from . import panda_cartesian
 from ._lib import PandasimError, lib
 from .core import PyBulletRobot, RobotTaskEnv, Task, TimeLimit
 from .envs import REGISTRY, PandaVecEnv, make
@@ -13,5 +14,5 @@ from .tasks import Flip, PickAndPlace, Push, Reach, Slide, Stack
 
 __all__ = ["make", "PandaVecEnv", "PandaSim", "REGISTRY", "PandasimError", "lib", "PyBulletRobot", "Task",
            "RobotTaskEnv", "TimeLimit", "Panda", "Reach", "Push", "PickAndPlace", "PandaReachEnv", "PandaPushEnv",
-           "PandaPickAndPlaceEnv", "Slide", "Stack", "Flip", "PandaSlideEnv", "PandaStackEnv", "PandaFlipEnv"]
+           "PandaPickAndPlaceEnv", "Slide", "Stack", "Flip", "PandaSlideEnv", "PandaStackEnv", "PandaFlipEnv", "panda_cartesian"]
 __version__ = "0.1.0"

@@ -69,13 +69,19 @@ def exported_symbols():
         "ps_step", "ps_sim_step", "ps_link_state", "ps_inverse_kinematics", "ps_compute_reward", "ps_rng_seed",
         "ps_rng_uniform", "ps_rng_rotation", "ps_base_state", "ps_camera", "ps_render", "ps_deproject_image",
         "ps_deproject_pixels", "ps_set_nonfinite_guard", "ps_set_lanes_per_env", "ps_step_lanes",
-        "ps_mark_motor_rows_dirty", "ps_set_episode_stats", *ORIENTED_SYMBOLS,
+        "ps_mark_motor_rows_dirty", "ps_set_episode_stats", *ORIENTED_SYMBOLS, *MOTION_SYMBOLS,
     ]
 
 
 # added within ABI version 6: a library built before them (one of the two that
 # scripts/compare_libs.py loads) still binds; calling one on it raises AttributeError
 ORIENTED_SYMBOLS = ("ps_step_oriented", "ps_euler_xyz_to_quat", "ps_quat_to_euler_xyz")
+# likewise the motion primitives (panda_cartesian.py move / grasp / release)
+MOTION_SYMBOLS = ("ps_motion_plan_bytes", "ps_plan_move", "ps_plan_grasp", "ps_plan_release", "ps_motion_run")
+# the motion plan's rows (include/pandasim.h PS_PLAN_*): f64 rows, then i32 rows, of the state's stride
+PLAN_START, PLAN_DELTA, PLAN_WIDTH, PLAN_Q0, PLAN_ROTVEC, PLAN_NUM_F64_ROWS = 0, 3, 6, 7, 11, 14
+PLAN_NUM_STEPS, PLAN_DONE, PLAN_BLOCKED, PLAN_KIND, PLAN_NUM_I32_ROWS = 0, 1, 2, 3, 4
+PLAN_KIND_MOVE, PLAN_KIND_HOLD, PLAN_HOLD_STEPS = 0, 1, 30
 
 
 def check_fresh(path: str) -> None:
@@ -149,13 +155,19 @@ def lib():
     L.ps_deproject_image.argtypes = [V, V, D, I, I, V, V, V, V]
     L.ps_deproject_pixels.argtypes = [V, V, V, I, D, I, I, V, V]
     for name in exported_symbols():
-        if name in ORIENTED_SYMBOLS and "PANDASIM_LIB" in os.environ and not hasattr(L, name):
+        if name in ORIENTED_SYMBOLS + MOTION_SYMBOLS and "PANDASIM_LIB" in os.environ and not hasattr(L, name):
             continue  # only a library named by PANDASIM_LIB may predate them
         if name == "ps_step_oriented":
             L.ps_step_oriented.argtypes = [V, V, V, V, V, V, V, V, V, V, I, V, V, V]
         elif name in ORIENTED_SYMBOLS:
             getattr(L, name).argtypes = [V, V, V, I64, V]
         getattr(L, name).restype = getattr(L, name).restype if name in ("ps_destroy", "ps_last_error") else I
+    if hasattr(L, "ps_motion_run"):
+        L.ps_motion_plan_bytes.argtypes, L.ps_motion_plan_bytes.restype = [I64], I64
+        L.ps_plan_move.argtypes = [V, V, V, V, V, V, V]
+        L.ps_plan_grasp.argtypes = [V, V, V, V, V]
+        L.ps_plan_release.argtypes = [V, V, V, V, V, V]
+        L.ps_motion_run.argtypes = [V, V, V, I, V]
     _lib = L
     return L
 

@@ -4,8 +4,9 @@ The library is linked from parallel hipcc jobs (csrc/ps_env.h): the C ABI and
 small kernels (pandasim.hip), the fused step kernels of each (task, control)
 pair (step_kernels.hip: the one-lane kernel, 12 objects, and the 16/8-lane
 group kernels, 10 objects -- Stack has none), the oriented step's kernels of
-each task at ee control (the same source with -DPS_STEP_ORI=1: 6 + 5 objects)
-and the plugin-path substep kernel of each scene (sim_kernels.hip, 4 objects).
+each task at ee control (the same source with -DPS_STEP_ORI=1: 6 + 5 objects),
+the plugin-path substep kernel of each scene (sim_kernels.hip, 4 objects) and
+the motion primitives' kernel of each scene (motion_kernels.hip, 4 objects).
 
 Every object is compiled with the same flags (-O3, no -mllvm scheduler
 options).  Round 3 built the group kernels at -O1 after an -O2/-O3 miscompute
@@ -62,6 +63,9 @@ UNITS = ([("pandasim", "pandasim.hip", [])]
              [f"-DPS_STEP_TASK={t}", "-DPS_STEP_CONTROL=0", "-DPS_STEP_ORI=1", "-DPS_STEP_GROUPS=1"])
             for t in range(6) if t != TASK_STACK]
          + [(f"sim_{n}_{s}", "sim_kernels.hip", [f"-DPS_SIM_NOBJ={n}", f"-DPS_SIM_SHAPE={s}"])
+            for n, s in ((0, 0), (1, 0), (1, 1), (2, 0))]
+         # ps_motion_run's kernel of each scene (k_motion, ps_motion.h): 4 objects
+         + [(f"motion_{n}_{s}", "motion_kernels.hip", [f"-DPS_MOTION_NOBJ={n}", f"-DPS_MOTION_SHAPE={s}"])
             for n, s in ((0, 0), (1, 0), (1, 1), (2, 0))])
 
 # diagnostic variants (never loaded by the product unless PANDASIM_LIB names them)

@@ -668,6 +668,70 @@ class PandaSim:
         self._call("ps_quat_to_euler_xyz", self._ctx, _ptr(flat), _ptr(out), flat.shape[0], self._stream())
         return out.reshape(*q.shape[:-1], 3)
 
+    # ---------------------------------------------------- motion primitives
+    # panda_cartesian.py:74-145 (move / grasp / release), fused: a plan call
+    # fills a MotionPlan from the state, motion_run executes its control steps
+    def motion_plan(self) -> "MotionPlan":
+        """A zeroed plan buffer of this batch (nothing to do, gripper free)."""
+        return MotionPlan(self)
+
+    def _mask(self, mask) -> Optional[torch.Tensor]:
+        if mask is None:
+            return None
+        m = torch.as_tensor(mask, device=self.device)
+        if m.shape != (self.num_envs,):
+            raise ValueError(f"mask: expected ({self.num_envs},), got {tuple(m.shape)}")
+        return (m != 0).to(torch.uint8).contiguous()
+
+    def plan_move(self, plan: "MotionPlan", goal_pos, goal_quat, mask=None) -> None:
+        """ps_plan_move: goal_pos [B, 3] or [3] world, goal_quat [B, 4] or [4] (x, y, z, w)."""
+        B = self.num_envs
+        pos = torch.as_tensor(goal_pos, dtype=torch.float32, device=self.device)
+        orn = torch.as_tensor(goal_quat, dtype=torch.float32, device=self.device)
+        if pos.shape not in ((3,), (B, 3)):
+            raise ValueError(f"goal_pos: expected (3,) or ({B}, 3), got {tuple(pos.shape)}")
+        if orn.shape not in ((4,), (B, 4)):
+            raise ValueError(f"goal_quat: expected (4,) or ({B}, 4), got {tuple(orn.shape)}")
+        pos, orn, m = pos.expand(B, 3).contiguous(), orn.expand(B, 4).contiguous(), self._mask(mask)
+        self._call("ps_plan_move", self._ctx, _ptr(self.state), _ptr(plan.buf), _ptr(pos), _ptr(orn), _ptr(m),
+                   self._stream())
+
+    def plan_grasp(self, plan: "MotionPlan", mask=None) -> None:
+        m = self._mask(mask)
+        self._call("ps_plan_grasp", self._ctx, _ptr(self.state), _ptr(plan.buf), _ptr(m), self._stream())
+
+    def plan_release(self, plan: "MotionPlan", width=None, mask=None) -> None:
+        """ps_plan_release: width a number or [B] (None = 1)."""
+        w = None
+        if width is not None:
+            w = torch.as_tensor(width, dtype=torch.float32, device=self.device).expand(self.num_envs).contiguous()
+        m = self._mask(mask)
+        self._call("ps_plan_release", self._ctx, _ptr(self.state), _ptr(plan.buf), _ptr(w), _ptr(m), self._stream())
+
+    def motion_run(self, plan: "MotionPlan", max_steps: int) -> None:
+        """ps_motion_run: every env runs min(max_steps, num_steps - done) control steps."""
+        self._call("ps_motion_run", self._ctx, _ptr(self.state), _ptr(plan.buf), int(max_steps), self._stream())
+
+
+class MotionPlan:
+    """The plan buffer of the motion primitives (include/pandasim.h PS_PLAN_*):
+    ``d`` [PLAN_NUM_F64_ROWS, stride] float64 and ``n`` [PLAN_NUM_I32_ROWS,
+    stride] int32 are views of ``buf``; num_steps / done / blocked are the
+    [B] views of their rows."""
+
+    def __init__(self, sim: PandaSim):
+        nbytes = sim._lib.ps_motion_plan_bytes(sim.num_envs)
+        if nbytes <= 0:
+            raise L.PandasimError("ps_motion_plan_bytes failed")
+        stride, B = sim.layout.stride, sim.num_envs
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=sim.device)
+        split = L.PLAN_NUM_F64_ROWS * stride * 8
+        self.d = self.buf[:split].view(torch.float64).view(L.PLAN_NUM_F64_ROWS, stride)
+        self.n = self.buf[split:].view(torch.int32).view(L.PLAN_NUM_I32_ROWS, stride)
+        self.num_steps = self.n[L.PLAN_NUM_STEPS, :B]
+        self.done = self.n[L.PLAN_DONE, :B]
+        self.blocked = self.n[L.PLAN_BLOCKED, :B]
+
 
 # ---------------------------------------------------------------- helpers
 PLANE_Z = -0.4                      # tasks/*.py: create_plane(z_offset=-0.4)

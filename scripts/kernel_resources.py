@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Register, scratch and LDS use of every step kernel of a built object or
+"""Register, scratch and LDS use of every step and motion kernel of a built object or
 library, from the code objects' AMDGPU metadata (no GPU needed).
 
 usage: python scripts/kernel_resources.py [lib or .o ...] [--json out.json]
@@ -66,13 +66,15 @@ def main(argv):
         out_json = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
     paths = argv or sorted(glob.glob(os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim",
-                                                  "step_*.o")))
+                                                  "step_*.o")) +
+                          glob.glob(os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim",
+                                                 "motion_*.o")))
     table = {}
     with tempfile.TemporaryDirectory() as tmp:
         for p in paths:
             for co in code_objects(p, tmp):
                 for k, v in kernels(co).items():
-                    if "k_step" in k or "k_sim_step" in k:
+                    if "k_step" in k or "k_sim_step" in k or "k_motion" in k:
                         table[demangle(k)] = v
     for k, v in sorted(table.items()):
         print(f"{k:40s} vgpr {v.get('vgpr_count', 0):3d} agpr {v.get('agpr_count', 0):3d} "

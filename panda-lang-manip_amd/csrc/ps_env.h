@@ -1,6 +1,7 @@
 // ps_env.h — the env layer shared by the kernel translation units of
 // libpandasim.so: the state view, task-layer device code (set_action, obs,
-// reward, reset) and the fused step / plugin-path substep kernels.  Each
+// reward, reset) and the fused step / plugin-path substep kernels, on top of
+// the physics headers ps_physics.h gathers (substep: ps_substep.h).  Each
 // step_kernels.hip object instantiates the step kernels of one (task,
 // control) pair and sim_kernels.hip those of one scene, so the library
 // builds as parallel hipcc jobs (pandasim/build.py); pandasim.hip holds the

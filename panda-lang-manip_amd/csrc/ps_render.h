@@ -12,7 +12,7 @@
 // matrix, 1 where nothing is hit.
 #pragma once
 
-#include "ps_physics.h"
+#include "ps_common.h"
 
 namespace ps {
 

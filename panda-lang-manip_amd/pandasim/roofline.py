@@ -2,7 +2,8 @@
 DESIGN.md §7).
 
 The cost of each primitive is counted from the formulas the step kernel
-evaluates (``csrc/ps_physics.h``, ``csrc/pandasim.hip``): an FMA is 2 FLOPs,
+evaluates (``csrc/ps_physics.h`` and the headers it gathers: kinematics,
+dynamics, collide, solver, substep; ``csrc/pandasim.hip``): an FMA is 2 FLOPs,
 add/sub/mul 1, div/sqrt/rsqrt/rcp/sin/cos/atan2 1 each; comparisons, min/max,
 selects and moves are not counted, and zero entries of the constant URDF
 origin rotations are counted as if they were not known (the algorithm's
@@ -14,7 +15,7 @@ own iteration count, not the wave-max the SIMD executes.
 """
 from __future__ import annotations
 
-# ---- per substep, independent of contacts (ps_physics.h substep())
+# ---- per substep, independent of contacts (ps_substep.h substep())
 FK = 7 * 83 + 3 * 63 + 2 * 84          # child_frame x 12 (revolute / fixed / prismatic)
 BIAS_FORCES = 7 * 357 + 2 * 63 + 250 + 2 * 370 + 7 * 23  # RNEA with fused FK: arm links, hand, fingers, tau
 GEOMETRY = FK + 30 + 8 * 21            # second FK, finger axes, 8 sphere centres

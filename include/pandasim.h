@@ -1,6 +1,7 @@
 /*
  * pandasim.h — C ABI of the MI355X-native batched Panda simulator
- * (libpandasim.so, built from panda-lang-manip_amd/csrc/pandasim.hip).
+ * (libpandasim.so, built from panda-lang-manip_amd/csrc: pandasim.hip and the
+ * kernel units).
  *
  * Drop-in boundary for the reference's step()/reset() path.  Each entry point
  * replaces one call site of /root/reference (cited per function); see

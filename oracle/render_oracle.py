@@ -31,7 +31,7 @@ import numpy as np
 import oracle as O
 
 # capsule proxies of the arm: (link frame index a or -1 = base origin, b, radius);
-# the hand bar is handled separately (same constants as csrc/pandasim.hip k_render_prep)
+# the hand bar is handled separately (same constants as csrc/render_kernels.hip k_render_prep)
 ARM_CAPSULES = [(-1, 0, 0.07), (1, 2, 0.065), (2, 3, 0.06), (3, 4, 0.06), (5, 6, 0.055), (6, 7, 0.05)]
 WRIST = (0.0, 0.0, 0.04)  # flange (link 8 origin) -> palm, in the hand frame, radius 0.045
 HAND_BAR = ((0.0, -0.09, 0.03), (0.0, 0.09, 0.03), 0.03)

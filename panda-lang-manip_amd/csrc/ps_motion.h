@@ -1,18 +1,12 @@
 // ps_motion.h — the Cartesian motion primitives of panda_cartesian.py:53-145
 // (move / grasp / release): the plan buffer's view, the arithmetic of one
 // control step and the fused run kernel k_motion.  motion_kernels.hip
-// instantiates k_motion once per scene, as sim_kernels.hip does k_sim_step;
-// pandasim.hip holds the plan kernels and the C ABI.
+// instantiates k_motion once per scene, as sim_kernels.hip does k_sim_step
+// (its launchers are declared with the others, ps_ctx.h); plan_kernels.hip
+// holds the plan kernels and their entry points, pandasim.hip ps_motion_run.
 #pragma once
 
 #include "ps_env.h"
-
-#define PS_MOTION_LAUNCHER_NAME_(NOBJ, SHAPE) ps_launch_motion_##NOBJ##_##SHAPE
-#define PS_MOTION_LAUNCHER_NAME(NOBJ, SHAPE) PS_MOTION_LAUNCHER_NAME_(NOBJ, SHAPE)
-#define PS_DECLARE_MOTION_LAUNCHER(NOBJ, SHAPE) \
-    int PS_MOTION_LAUNCHER_NAME(NOBJ, SHAPE)(ps_ctx * c, void *state, void *plan, int max_steps, hipStream_t st);
-PS_DECLARE_MOTION_LAUNCHER(0, 0) PS_DECLARE_MOTION_LAUNCHER(1, 0) PS_DECLARE_MOTION_LAUNCHER(1, 1)
-PS_DECLARE_MOTION_LAUNCHER(2, 0)
 
 namespace {
 
@@ -91,7 +85,7 @@ PS_D int move_num_steps(double d) {
 // the action clipped to [-1, 1], target = ee position + action[:3] with z >= 0
 // (fp64, rounded once to f32 for IK), the fingers' target 0 when blocked, else
 // the current width + action[3], POSITION_CONTROL defaults as set_action of
-// ps_env.h.
+// ps_task.h.
 PS_D void motion_step_target(const Scene &sc, const PlanView &pl, int64_t i, int istep, int num, int kind,
                              const Kin &k, V3 &target, Q4 &orn, float &a_width) {
 #pragma clang fp contract(off)

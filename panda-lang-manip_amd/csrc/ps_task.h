@@ -1,163 +1,274 @@
-// ps_task.h — device restatement of the task layer:
-//   numpy SeedSequence + PCG64 + Generator.uniform (gymnasium seeding,
-//   panda_gym/envs/core.py:244), goal/object sampling (reach.py:47-54,
-//   push.py:69-87, pick_and_place.py:65-85), the fp64 distance / success /
-//   reward (utils.py:4-15, push.py:89-98) and getEulerFromQuaternion.
-// Integer work is exact; the fp64 arithmetic uses explicit round-to-nearest
-// intrinsics (no FMA contraction) so results are bit-identical to numpy.
+// ps_task.h — device restatement of the task layer (panda_gym tasks/*.py,
+// envs/core.py, envs/robots/panda.py) on the state view: the per-task
+// constants, the observation and achieved goal, the fp64 distance / success /
+// reward (utils.py:4-15), the goal and object draws of a reset with Flip's
+// splitmix64 goal stream, and Panda.set_action.  The random stream itself is
+// ps_task_rng.h.
 #pragma once
 
-#include "ps_common.h"
+#include "ps_dynamics.h"
+#include "ps_state.h"
 
-namespace ps {
+namespace {
 
-struct Pcg {
-    uint64_t sh, sl, ih, il;  // state hi/lo, increment hi/lo
+// Per-task constants (panda_gym/__init__.py:8-54, envs/panda_tasks.py:14-113,
+// tasks/*.py): objects, shape, goal size, TimeLimit and success threshold.
+template <int TASK>
+struct TaskTraits {
+    static constexpr int NOBJ = TASK == PS_TASK_REACH ? 0 : (TASK == PS_TASK_STACK ? 2 : 1);
+    static constexpr int SHAPE = TASK == PS_TASK_SLIDE ? PS_SHAPE_CYLINDER : PS_SHAPE_BOX;
+    static constexpr int GOAL = TASK == PS_TASK_STACK ? 6 : (TASK == PS_TASK_FLIP ? 4 : 3);
+    static constexpr int STEPS = TASK == PS_TASK_STACK ? PM_STACK_MAX_EPISODE_STEPS : PM_MAX_EPISODE_STEPS;
+    static constexpr double THRESHOLD = TASK == PS_TASK_STACK ? PM_STACK_DISTANCE_THRESHOLD
+                                        : TASK == PS_TASK_FLIP ? PM_FLIP_DISTANCE_THRESHOLD
+                                                               : PM_DISTANCE_THRESHOLD;
 };
 
-PS_D void pcg_step(Pcg &r) {
-    const uint64_t MH = 0x2360ED051FC65DA4ULL, ML = 0x4385DF649FCCF645ULL;
-    uint64_t lo = r.sl * ML;
-    uint64_t hi = __umul64hi(r.sl, ML) + r.sl * MH + r.sh * ML;
-    uint64_t nl = lo + r.il;
-    uint64_t carry = nl < lo ? 1ULL : 0ULL;
-    r.sh = hi + r.ih + carry;
-    r.sl = nl;
-}
-
-PS_D uint64_t pcg_next(Pcg &r) {
-    pcg_step(r);
-    uint64_t x = r.sh ^ r.sl;
-    unsigned rot = (unsigned)(r.sh >> 58);
-    return (x >> rot) | (x << ((64u - rot) & 63u));
-}
-
-// Opaque barriers: hipcc contracts a*b+c into an FMA across inlined helper
-// calls even under `#pragma clang fp contract(off)`; numpy rounds the product
-// first.  An empty asm on the product keeps it a separate, rounded value.
-PS_D double opaque(double x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-PS_D float opaque(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
-PS_D double pcg_double(Pcg &r) { return __dmul_rn((double)(pcg_next(r) >> 11), 1.0 / 9007199254740992.0); }
-
-// Generator.uniform: low + (high - low) * next_double
-PS_D double uniform(Pcg &r, double lo, double hi) {
-#pragma clang fp contract(off)
-    double range = __dsub_rn(hi, lo);
-    double u = pcg_double(r);
-    return __dadd_rn(lo, opaque(__dmul_rn(range, u)));
-}
-
-// SeedSequence(seed).generate_state(4, uint64) -> pcg64_set_seed
-PS_D Pcg pcg_seed(uint64_t seed) {
-    const uint32_t INIT_A = 0x43b0d7e5u, MULT_A = 0x931e8875u, INIT_B = 0x8b51f9ddu, MULT_B = 0x58f38dedu;
-    const uint32_t MIX_L = 0xca01f9ddu, MIX_R = 0x4973f715u;
-    uint32_t e0 = (uint32_t)seed, e1 = (uint32_t)(seed >> 32);
-    int nent = (seed >> 32) ? 2 : 1;
-    uint32_t pool[4], hc = INIT_A;
+// ------------------------------------------------------- task layer pieces
+// ee = grasptarget (link 11; COM == link frame): position and COM velocity
+PS_D void ee_state(const Scene &sc, const float q[9], const float qd[9], V3 &pos, V3 &vel) {
+    Kin k;
+    fk(q, k);
+    V3 p = k.f[11].o;
+    V3 v = mk(0, 0, 0);
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        uint32_t v = (i == 0 ? e0 : (i == 1 && nent == 2 ? e1 : 0u)) ^ hc;
-        hc *= MULT_A;
-        v *= hc;
-        v ^= v >> 16;
-        pool[i] = v;
+    for (int d = 0; d < 7; d++) v = v + cross(col(k.f[d].R, 2), p - k.f[d].o) * qd[d];
+    pos = p + sc.base;
+    vel = v;
+}
+
+// RobotTaskEnv._get_obs (core.py:229-238): robot obs (panda.py:109-119), the
+// task obs (push.py:49-63; stack.py:65-91 both objects; flip.py:53-60 with the
+// quaternion in place of Euler angles) and the achieved goal
+template <int TASK>
+PS_D void write_obs(const KParams &P, int64_t i, const float q[9], const float qd[9], const Body *bd,
+                    const double g[6], float *obs, float *ag, float *dg) {
+    using T = TaskTraits<TASK>;
+    V3 p, v;
+    ee_state(P.sc, q, qd, p, v);
+    float o[31];
+    o[0] = p.x; o[1] = p.y; o[2] = p.z;
+    o[3] = v.x; o[4] = v.y; o[5] = v.z;
+    int k = 6;
+    if (!P.block_gripper) o[k++] = q[7] + q[8];
+#pragma unroll
+    for (int b = 0; b < T::NOBJ; b++) {
+        const Body &cb = bd[b];
+        o[k] = cb.pos.x; o[k + 1] = cb.pos.y; o[k + 2] = cb.pos.z;
+        k += 3;
+        if constexpr (TASK == PS_TASK_FLIP) {
+            o[k] = cb.quat.x; o[k + 1] = cb.quat.y; o[k + 2] = cb.quat.z; o[k + 3] = cb.quat.w;
+            k += 4;
+        } else {
+            V3 e = euler_from_quat(cb.quat);
+            o[k] = e.x; o[k + 1] = e.y; o[k + 2] = e.z;
+            k += 3;
+        }
+        o[k] = cb.vel.x; o[k + 1] = cb.vel.y; o[k + 2] = cb.vel.z;
+        o[k + 3] = cb.omg.x; o[k + 4] = cb.omg.y; o[k + 5] = cb.omg.z;
+        k += 6;
     }
-#pragma unroll
-    for (int s = 0; s < 4; s++)
-#pragma unroll
-        for (int d = 0; d < 4; d++)
-            if (s != d) {
-                uint32_t v = pool[s] ^ hc;
-                hc *= MULT_A;
-                v *= hc;
-                v ^= v >> 16;
-                uint32_t r = MIX_L * pool[d] - MIX_R * v;
-                r ^= r >> 16;
-                pool[d] = r;
-            }
-    uint32_t w[8], hb = INIT_B;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint32_t v = pool[i & 3] ^ hb;
-        hb *= MULT_B;
-        v *= hb;
-        v ^= v >> 16;
-        w[i] = v;
+    float a[6];
+    if constexpr (TASK == PS_TASK_REACH) {
+        a[0] = p.x; a[1] = p.y; a[2] = p.z;
+    } else if constexpr (TASK == PS_TASK_FLIP) {
+        a[0] = bd[0].quat.x; a[1] = bd[0].quat.y; a[2] = bd[0].quat.z; a[3] = bd[0].quat.w;
+    } else {
+        a[0] = bd[0].pos.x; a[1] = bd[0].pos.y; a[2] = bd[0].pos.z;
+        if constexpr (T::NOBJ == 2) { a[3] = bd[1].pos.x; a[4] = bd[1].pos.y; a[5] = bd[1].pos.z; }
     }
-    uint64_t v0 = (uint64_t)w[0] | ((uint64_t)w[1] << 32), v1 = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-    uint64_t v2 = (uint64_t)w[4] | ((uint64_t)w[5] << 32), v3 = (uint64_t)w[6] | ((uint64_t)w[7] << 32);
-    Pcg r;
-    // inc = (initseq << 1) | 1 with initseq = v2:v3
-    r.ih = (v2 << 1) | (v3 >> 63);
-    r.il = (v3 << 1) | 1ULL;
-    r.sh = 0;
-    r.sl = 0;
-    pcg_step(r);
-    // state += initstate (v0:v1)
-    uint64_t nl = r.sl + v1;
-    r.sh = r.sh + v0 + (nl < r.sl ? 1ULL : 0ULL);
-    r.sl = nl;
-    pcg_step(r);
-    return r;
+    if (obs) {
+#pragma unroll
+        for (int j = 0; j < 31; j++)
+            if (j < P.obs_dim) obs[i * P.obs_dim + j] = o[j];
+    }
+    if (ag) {
+#pragma unroll
+        for (int j = 0; j < T::GOAL; j++) ag[i * T::GOAL + j] = a[j];
+    }
+    if (dg) {
+#pragma unroll
+        for (int j = 0; j < T::GOAL; j++) dg[i * T::GOAL + j] = __double2float_rn(g[j]);
+    }
 }
 
-// d = || float(ag) - goal ||_2 in fp64, summed left to right as numpy does
-PS_D double goal_distance(float a0, float a1, float a2, double g0, double g1, double g2) {
+// achieved goal of the stepped state (float32, as _get_obs casts it)
+template <int TASK>
+PS_D void achieved(const KParams &P, const float q[9], const float qd[9], const Body *bd, float a[6]) {
+    if constexpr (TASK == PS_TASK_REACH) {
+        V3 p, v;
+        ee_state(P.sc, q, qd, p, v);
+        a[0] = p.x; a[1] = p.y; a[2] = p.z;
+    } else if constexpr (TASK == PS_TASK_FLIP) {
+        a[0] = bd[0].quat.x; a[1] = bd[0].quat.y; a[2] = bd[0].quat.z; a[3] = bd[0].quat.w;
+    } else {
+        a[0] = bd[0].pos.x; a[1] = bd[0].pos.y; a[2] = bd[0].pos.z;
+        if constexpr (TaskTraits<TASK>::NOBJ == 2) { a[3] = bd[1].pos.x; a[4] = bd[1].pos.y; a[5] = bd[1].pos.z; }
+    }
+}
+
+// utils.distance (3 or 6 values) / utils.angle_distance (Flip) of float32
+// achieved vs float64 desired, in float64 as numpy promotes
+template <int TASK>
+PS_D double goal_metric(const float a[6], const double g[6]) {
 #pragma clang fp contract(off)
-    double d0 = __dsub_rn((double)a0, g0), d1 = __dsub_rn((double)a1, g1), d2 = __dsub_rn((double)a2, g2);
-    double s = opaque(__dmul_rn(d0, d0));
-    s = __dadd_rn(s, opaque(__dmul_rn(d1, d1)));
-    s = __dadd_rn(s, opaque(__dmul_rn(d2, d2)));
-    return __dsqrt_rn(s);
+    if constexpr (TASK == PS_TASK_FLIP) {
+        double dot = opaque(__dmul_rn((double)a[0], g[0]));
+#pragma unroll
+        for (int k = 1; k < 4; k++) dot = __dadd_rn(dot, opaque(__dmul_rn((double)a[k], g[k])));
+        return __dsub_rn(1.0, opaque(__dmul_rn(dot, dot)));
+    } else {
+        constexpr int N = TaskTraits<TASK>::GOAL;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            double e = __dsub_rn((double)a[k], g[k]);
+            double e2 = opaque(__dmul_rn(e, e));
+            s = k == 0 ? e2 : __dadd_rn(s, e2);
+        }
+        return __dsqrt_rn(s);
+    }
 }
 
-PS_D double goal_distance_f64(double a0, double a1, double a2, double g0, double g1, double g2) {
-#pragma clang fp contract(off)
-    double d0 = __dsub_rn(a0, g0), d1 = __dsub_rn(a1, g1), d2 = __dsub_rn(a2, g2);
-    double s = opaque(__dmul_rn(d0, d0));
-    s = __dadd_rn(s, opaque(__dmul_rn(d1, d1)));
-    s = __dadd_rn(s, opaque(__dmul_rn(d2, d2)));
-    return __dsqrt_rn(s);
-}
-
-PS_D float reward_of(int reward_type, double d) {
-    if (reward_type == 0) return d > PM_DISTANCE_THRESHOLD ? -1.0f : -0.0f;
+PS_D float reward_for(int reward_type, double d, double thr) {
+    if (reward_type == 0) return d > thr ? -1.0f : -0.0f;
     return -__double2float_rn(d);
 }
 
-// all-float32 operands: numpy keeps the arithmetic and the comparison with the
-// Python-float threshold in float32 (the threshold becomes 0.05f)
-PS_D float goal_distance_f32(float a0, float a1, float a2, float g0, float g1, float g2) {
+// splitmix64 stream of Flip's goal (oracle po_flip_goal): R.random()
+// (flip.py:70-72) as a uniform unit quaternion by Marsaglia's method -- two
+// rejection-sampled points of the unit disc, q = (x1, x2, x3 t, x4 t),
+// t = sqrt((1 - s1) / s2).  Only correctly rounded +, *, / and sqrt, kept
+// uncontracted, so the oracle's draws are reproduced bit for bit.
+PS_D uint64_t splitmix64(uint64_t &st) {
+    uint64_t z = (st += 0x9E3779B97F4A7C15ULL);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+PS_D uint64_t aux_seed(uint64_t seed) { return seed ^ 0x5851F42D4C957F2DULL; }
+PS_D double aux_signed_unit(uint64_t &st) {
 #pragma clang fp contract(off)
-    float d0 = __fsub_rn(a0, g0), d1 = __fsub_rn(a1, g1), d2 = __fsub_rn(a2, g2);
-    float s = opaque(__fmul_rn(d0, d0));
-    s = __fadd_rn(s, opaque(__fmul_rn(d1, d1)));
-    s = __fadd_rn(s, opaque(__fmul_rn(d2, d2)));
-    // correctly rounded fp32 sqrt: the fp64 root rounded once to fp32 is
-    // exact-rounded for sqrt (53 >= 2*24 + 2); v_sqrt_f32 alone is not
-    return __double2float_rn(__dsqrt_rn((double)s));
+    return __dsub_rn(opaque(__dmul_rn((double)(splitmix64(st) >> 11), 2.0 / 9007199254740992.0)), 1.0);
+}
+PS_D double disc_point(uint64_t &st, double &x, double &y) {
+#pragma clang fp contract(off)
+    for (;;) {
+        x = aux_signed_unit(st);
+        y = aux_signed_unit(st);
+        double s = __dadd_rn(opaque(__dmul_rn(x, x)), opaque(__dmul_rn(y, y)));
+        if (s < 1.0 && s > 0.0) return s;
+    }
+}
+PS_D void random_rotation(uint64_t &st, double q[4]) {
+#pragma clang fp contract(off)
+    double x1, x2, x3, x4;
+    double s1 = disc_point(st, x1, x2);
+    double s2 = disc_point(st, x3, x4);
+    double t = __dsqrt_rn(__ddiv_rn(__dsub_rn(1.0, s1), s2));
+    q[0] = x1;
+    q[1] = x2;
+    q[2] = __dmul_rn(x3, t);
+    q[3] = __dmul_rn(x4, t);
 }
 
-PS_D float reward_of_f32(int reward_type, float d) {
-    if (reward_type == 0) return d > (float)PM_DISTANCE_THRESHOLD ? -1.0f : -0.0f;
-    return -d;
+// set_base_pose -> resetBasePositionAndOrientation (pybullet.py:427-439):
+// PyBullet's init-pose command sets the base pose and, with it, zero base
+// linear and angular velocity
+PS_D void place(Body &b, double x, double y, double z) {
+    b.pos = mk((float)x, (float)y, (float)z);
+    b.quat = Q4{0.0f, 0.0f, 0.0f, 1.0f};
+    b.vel = mk(0.0f, 0.0f, 0.0f);
+    b.omg = mk(0.0f, 0.0f, 0.0f);
 }
 
-// getEulerFromQuaternion (fp32)
-PS_D V3 euler_from_quat(Q4 q) {
-    float sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
-    float sarg = -2.0f * (q.x * q.z - q.w * q.y);
-    if (sarg <= -0.99999f) return mk(0.0f, -0.5f * 3.14159265358979323846f, 2.0f * atan2f(q.x, -q.y));
-    if (sarg >= 0.99999f) return mk(0.0f, 0.5f * 3.14159265358979323846f, 2.0f * atan2f(-q.x, q.y));
-    return mk(atan2f(2.0f * (q.y * q.z + q.w * q.x), squ - sqx - sqy + sqz), asinf(sarg),
-              atan2f(2.0f * (q.x * q.y + q.w * q.z), squ + sqx - sqy - sqz));
+// Panda.reset + Task.reset (core.py:245-247): goal then object draws in the
+// reference's order (reach.py:47-54, push.py:69-87, pick_and_place.py:65-85,
+// slide.py:69-87, stack.py:103-116, flip.py:66-78)
+template <int TASK>
+PS_D void reset_env(float q[9], float qd[9], Body *bd, double g[6], Pcg &r, uint64_t &aux) {
+#pragma unroll
+    for (int d = 0; d < 9; d++) {
+        q[d] = (float)neutral_q(d);
+        qd[d] = 0.0f;
+    }
+    constexpr double xy = 0.3 / 2;  // goal_xy_range / 2 = obj_xy_range / 2
+    if constexpr (TASK == PS_TASK_REACH) {
+        g[0] = uniform(r, -xy, xy);
+        g[1] = uniform(r, -xy, xy);
+        g[2] = uniform(r, 0.0, 0.3);
+    } else if constexpr (TASK == PS_TASK_STACK) {
+        constexpr double size = PM_OBJECT_SIZE;
+        double n0 = uniform(r, -xy, xy), n1 = uniform(r, -xy, xy), n2 = uniform(r, 0.0, 0.0);
+        g[0] = __dadd_rn(0.0, n0);
+        g[1] = __dadd_rn(0.0, n1);
+        g[2] = __dadd_rn(size / 2, n2);
+        g[3] = __dadd_rn(0.0, n0);
+        g[4] = __dadd_rn(0.0, n1);
+        g[5] = __dadd_rn(3 * size / 2, n2);
+        double a0 = uniform(r, -xy, xy), a1 = uniform(r, -xy, xy), a2 = uniform(r, 0.0, 0.0);
+        double b0 = uniform(r, -xy, xy), b1 = uniform(r, -xy, xy), b2 = uniform(r, 0.0, 0.0);
+        place(bd[0], __dadd_rn(0.0, a0), __dadd_rn(0.0, a1), __dadd_rn(size / 2, a2));
+        place(bd[1], __dadd_rn(0.0, b0), __dadd_rn(0.0, b1), __dadd_rn(3 * size / 2, b2));
+    } else if constexpr (TASK == PS_TASK_FLIP) {
+        random_rotation(aux, g);
+        double o0 = uniform(r, -xy, xy), o1 = uniform(r, -xy, xy), o2 = uniform(r, 0.0, 0.0);
+        place(bd[0], __dadd_rn(0.0, o0), __dadd_rn(0.0, o1), __dadd_rn(PM_OBJECT_SIZE / 2, o2));
+    } else {
+        // Push, PickAndPlace, Slide
+        constexpr double size = TASK == PS_TASK_SLIDE ? PM_SLIDE_OBJECT_SIZE : PM_OBJECT_SIZE;
+        constexpr double gx = TASK == PS_TASK_SLIDE ? PM_SLIDE_GOAL_X_OFFSET : 0.0;
+        constexpr double zr = TASK == PS_TASK_PICK_AND_PLACE ? 0.2 : 0.0;
+        double n0 = uniform(r, -xy + gx, xy + gx), n1 = uniform(r, -xy, xy), n2 = uniform(r, 0.0, zr);
+        if (TASK == PS_TASK_PICK_AND_PLACE && pcg_double(r) < 0.3) n2 = 0.0;
+        g[0] = __dadd_rn(0.0, n0);
+        g[1] = __dadd_rn(0.0, n1);
+        g[2] = __dadd_rn(size / 2, n2);
+        double o0 = uniform(r, -xy, xy), o1 = uniform(r, -xy, xy), o2 = uniform(r, 0.0, 0.0);
+        place(bd[0], __dadd_rn(0.0, o0), __dadd_rn(0.0, o1), __dadd_rn(size / 2, o2));
+    }
 }
 
-}  // namespace ps
+// Panda.set_action (panda.py:52-107) -> motor targets (control_joints).
+// ORI (ee control; panda_ori.py:52-99): the IK target's orientation is the
+// env's quaternion orn[4] (x, y, z, w; inverse_kinematics normalises it) in
+// place of the standard one, which stays a compile-time constant otherwise.
+template <int CONTROL, bool ORI = false>
+PS_D void set_action(const KParams &P, const float *act, const float q[9], Motors &m, const float *orn = nullptr) {
+    float a[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) a[j] = j < P.action_dim ? fminf(fmaxf(act[j], -1.0f), 1.0f) : 0.0f;
+    float tq[9];
+    if constexpr (CONTROL == PS_CONTROL_EE) {
+        V3 p, v;
+        float zero[9];
+#pragma unroll
+        for (int d = 0; d < 9; d++) zero[d] = 0.0f;
+        ee_state(P.sc, q, zero, p, v);
+        V3 t = p + mk(a[0] * 0.05f, a[1] * 0.05f, a[2] * 0.05f);
+        t.z = fmaxf(0.0f, t.z);
+        float qik[9];
+        if constexpr (ORI)
+            inverse_kinematics<11>(q, t - P.sc.base, Q4{orn[0], orn[1], orn[2], orn[3]}, qik);
+        else
+            inverse_kinematics<11>(q, t - P.sc.base, Q4{1.0f, 0.0f, 0.0f, 0.0f}, qik);
+#pragma unroll
+        for (int d = 0; d < 7; d++) tq[d] = qik[d];
+    } else {
+#pragma unroll
+        for (int d = 0; d < 7; d++) tq[d] = q[d] + a[d] * 0.05f;
+    }
+    float width = 0.0f;
+    if (!P.block_gripper) width = (q[7] + q[8]) + a[P.action_dim - 1] * 0.2f;
+    tq[7] = tq[8] = width * 0.5f;
+#pragma unroll
+    for (int d = 0; d < 9; d++) {
+        m.target[d] = tq[d];
+        m.kp[d] = (float)PM_MOTOR_KP;
+        m.kd[d] = (float)PM_MOTOR_KD;
+        m.vel[d] = 0.0f;
+        m.imp[d] = (float)(joint_force(d) * PM_TIMESTEP);
+    }
+}
+
+}  // namespace

@@ -1,4 +1,4 @@
-// sim_kernels.hip — the plugin path's substep kernel (k_sim_step, ps_env.h)
+// sim_kernels.hip — the plugin path's substep kernel (k_sim_step, ps_step.h)
 // of one scene: built once per (objects, shape) with -DPS_SIM_NOBJ=n
 // -DPS_SIM_SHAPE=s (pandasim/build.py).  ps_sim_step (pandasim.hip) calls it.
 #include "ps_env.h"

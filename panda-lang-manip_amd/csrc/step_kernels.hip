@@ -1,4 +1,4 @@
-// step_kernels.hip — the fused step kernels (k_step, ps_env.h) of one
+// step_kernels.hip — the fused step kernels (k_step, ps_step.h) of one
 // (task, control) pair: built once per pair with -DPS_STEP_TASK=t
 // -DPS_STEP_CONTROL=c (pandasim/build.py), so the pairs compile as parallel
 // jobs.  ps_step (pandasim.hip) calls the pair's launcher.  The one-lane
@@ -32,7 +32,7 @@
                        io.truncated, io.final_obs, io.final_ag, io.orn)
 
 #if defined(PS_STEP_GROUPS) && PS_STEP_GROUPS
-static_assert(PS_STEP_TASK != PS_TASK_STACK, "Stack has no group kernels (two objects: 21 DoFs)");
+static_assert(task_has_groups(PS_STEP_TASK), "Stack has no group kernels (two objects: 21 DoFs)");
 
 int PS_THIS_GROUP_LAUNCHER(ps_ctx *c, const void *params, const ps_step_io &io, int lanes, hipStream_t st) {
     const KParams P = *static_cast<const KParams *>(params);
@@ -50,10 +50,11 @@ int PS_THIS_LAUNCHER(ps_ctx *c, void *state, const ps_step_io &io, int lanes, hi
     // the gain rows belong to a state buffer: another buffer than the one the
     // last step wrote (a swapped or copied-in state) gets them written too
     P.write_gains = c->gains_dirty || state != c->gains_state;
-    // groups of 16 or 8 lanes per env exist for the one-object and robot-only tasks
-#if PS_STEP_TASK != 4  // PS_TASK_STACK
-    if (lanes == 16 || lanes == 8) return PS_THIS_GROUP_LAUNCHER(c, &P, io, lanes, st);
-#endif
+    // groups of 16 or 8 lanes per env exist for the one-object and robot-only
+    // tasks (PS_FOR_EACH_GROUP_TASK, ps_ctx.h)
+    if constexpr (task_has_groups(PS_STEP_TASK)) {
+        if (lanes == 16 || lanes == 8) return PS_THIS_GROUP_LAUNCHER(c, &P, io, lanes, st);
+    }
     PS_LAUNCH(1);
     return check_launch(c);
 }

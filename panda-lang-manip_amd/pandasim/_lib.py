@@ -62,22 +62,63 @@ class PandasimError(RuntimeError):
 _lib = None
 
 
-def exported_symbols():
-    return [
-        "ps_abi_version", "ps_default_config", "ps_state_layout", "ps_create", "ps_destroy", "ps_last_error",
-        "ps_obs_dim", "ps_action_dim", "ps_goal_dim", "ps_max_episode_steps", "ps_init_state", "ps_reset",
-        "ps_step", "ps_sim_step", "ps_link_state", "ps_inverse_kinematics", "ps_compute_reward", "ps_rng_seed",
-        "ps_rng_uniform", "ps_rng_rotation", "ps_base_state", "ps_camera", "ps_render", "ps_deproject_image",
-        "ps_deproject_pixels", "ps_set_nonfinite_guard", "ps_set_lanes_per_env", "ps_step_lanes",
-        "ps_mark_motor_rows_dirty", "ps_set_episode_stats", *ORIENTED_SYMBOLS, *MOTION_SYMBOLS,
-    ]
-
-
+V, I, I64, P = C.c_void_p, C.c_int, C.c_int64, C.POINTER
+F, D = P(C.c_float), P(C.c_double)
+# Every exported symbol (include/pandasim.h), once: name -> (argtypes, restype,
+# group).  argtypes None leaves the ctypes default.  A group names symbols
 # added within ABI version 6: a library built before them (one of the two that
-# scripts/compare_libs.py loads) still binds; calling one on it raises AttributeError
-ORIENTED_SYMBOLS = ("ps_step_oriented", "ps_euler_xyz_to_quat", "ps_quat_to_euler_xyz")
-# likewise the motion primitives (panda_cartesian.py move / grasp / release)
-MOTION_SYMBOLS = ("ps_motion_plan_bytes", "ps_plan_move", "ps_plan_grasp", "ps_plan_release", "ps_motion_run")
+# scripts/compare_libs.py loads under PANDASIM_LIB) still binds, and calling
+# one on it raises AttributeError -- "oriented" the oriented step, "motion" the
+# motion primitives (panda_cartesian.py move / grasp / release).
+SIGNATURES = {
+    "ps_abi_version": (None, I, None),
+    "ps_default_config": ([I, I, I, P(Config)], I, None),
+    "ps_state_layout": ([I64, P(Layout)], I, None),
+    "ps_create": ([P(Config), I64, I, P(V)], I, None),
+    "ps_destroy": ([V], None, None),
+    "ps_last_error": ([V], C.c_char_p, None),
+    "ps_obs_dim": ([V], I, None),
+    "ps_action_dim": ([V], I, None),
+    "ps_goal_dim": ([V], I, None),
+    "ps_max_episode_steps": ([V], I, None),
+    "ps_init_state": ([V, V, V], I, None),
+    "ps_reset": ([V, V, V, V, V, V, V, V], I, None),
+    "ps_step": ([V, V, V, V, V, V, V, V, V, I, V, V, V], I, None),
+    "ps_sim_step": ([V, V, I, V], I, None),
+    "ps_link_state": ([V, V, I, V, V, V, V, V], I, None),
+    "ps_inverse_kinematics": ([V, V, I, V, V, V, V], I, None),
+    "ps_compute_reward": ([I, I, V, I, V, I, V, V, I64, V], I, None),
+    "ps_rng_seed": ([V, V, V, V, V], I, None),
+    "ps_rng_uniform": ([V, V, V, I, D, D, V, V], I, None),
+    "ps_rng_rotation": ([V, V, V, V, V], I, None),
+    "ps_base_state": ([V, V, I, V, V, V, V, V, V], I, None),
+    "ps_camera": ([F, C.c_float, C.c_float, C.c_float, C.c_float, I, I, F, F, D], I, None),
+    "ps_render": ([V, V, F, F, I, I, P(Visual), V, V, V, V], I, None),
+    "ps_deproject_image": ([V, V, D, I, I, V, V, V, V], I, None),
+    "ps_deproject_pixels": ([V, V, V, I, D, I, I, V, V], I, None),
+    "ps_set_nonfinite_guard": ([V, V, I], I, None),
+    "ps_set_lanes_per_env": ([V, I], I, None),
+    "ps_step_lanes": ([V], I, None),
+    "ps_mark_motor_rows_dirty": ([V], I, None),
+    "ps_set_episode_stats": ([V, V], I, None),
+    "ps_step_oriented": ([V, V, V, V, V, V, V, V, V, V, I, V, V, V], I, "oriented"),
+    "ps_euler_xyz_to_quat": ([V, V, V, I64, V], I, "oriented"),
+    "ps_quat_to_euler_xyz": ([V, V, V, I64, V], I, "oriented"),
+    "ps_motion_plan_bytes": ([I64], I64, "motion"),
+    "ps_plan_move": ([V, V, V, V, V, V, V], I, "motion"),
+    "ps_plan_grasp": ([V, V, V, V, V], I, "motion"),
+    "ps_plan_release": ([V, V, V, V, V, V], I, "motion"),
+    "ps_motion_run": ([V, V, V, I, V], I, "motion"),
+}
+ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
+MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
+
+
+def exported_symbols():
+    return list(SIGNATURES)
+
+
+
 # the motion plan's rows (include/pandasim.h PS_PLAN_*): f64 rows, then i32 rows, of the state's stride
 PLAN_START, PLAN_DELTA, PLAN_WIDTH, PLAN_Q0, PLAN_ROTVEC, PLAN_NUM_F64_ROWS = 0, 3, 6, 7, 11, 14
 PLAN_NUM_STEPS, PLAN_DONE, PLAN_BLOCKED, PLAN_KIND, PLAN_NUM_I32_ROWS = 0, 1, 2, 3, 4
@@ -120,54 +161,13 @@ def lib():
         raise PandasimError(f"{LIB_PATH} not found: build it with `python -m pandasim.build` (hipcc, gfx950)")
     check_fresh(LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    V, I, I64, P = C.c_void_p, C.c_int, C.c_int64, C.POINTER
-    L.ps_abi_version.restype = I
-    L.ps_default_config.argtypes = [I, I, I, P(Config)]
-    L.ps_state_layout.argtypes = [I64, P(Layout)]
-    L.ps_create.argtypes = [P(Config), I64, I, P(V)]
-    L.ps_destroy.argtypes = [V]
-    L.ps_destroy.restype = None
-    L.ps_last_error.argtypes = [V]
-    L.ps_last_error.restype = C.c_char_p
-    L.ps_obs_dim.argtypes = [V]
-    L.ps_action_dim.argtypes = [V]
-    L.ps_goal_dim.argtypes = [V]
-    L.ps_max_episode_steps.argtypes = [V]
-    L.ps_init_state.argtypes = [V, V, V]
-    L.ps_reset.argtypes = [V, V, V, V, V, V, V, V]
-    L.ps_step.argtypes = [V, V, V, V, V, V, V, V, V, I, V, V, V]
-    L.ps_sim_step.argtypes = [V, V, I, V]
-    L.ps_set_nonfinite_guard.argtypes = [V, V, I]
-    L.ps_set_lanes_per_env.argtypes = [V, I]
-    L.ps_step_lanes.argtypes = [V]
-    L.ps_mark_motor_rows_dirty.argtypes = [V]
-    L.ps_set_episode_stats.argtypes = [V, V]
-    L.ps_link_state.argtypes = [V, V, I, V, V, V, V, V]
-    L.ps_inverse_kinematics.argtypes = [V, V, I, V, V, V, V]
-    L.ps_compute_reward.argtypes = [I, I, V, I, V, I, V, V, I64, V]
-    L.ps_rng_seed.argtypes = [V, V, V, V, V]
-    L.ps_rng_uniform.argtypes = [V, V, V, I, P(C.c_double), P(C.c_double), V, V]
-    L.ps_rng_rotation.argtypes = [V, V, V, V, V]
-    L.ps_base_state.argtypes = [V, V, I, V, V, V, V, V, V]
-    F, D = P(C.c_float), P(C.c_double)
-    L.ps_camera.argtypes = [F, C.c_float, C.c_float, C.c_float, C.c_float, I, I, F, F, D]
-    L.ps_render.argtypes = [V, V, F, F, I, I, P(Visual), V, V, V, V]
-    L.ps_deproject_image.argtypes = [V, V, D, I, I, V, V, V, V]
-    L.ps_deproject_pixels.argtypes = [V, V, V, I, D, I, I, V, V]
-    for name in exported_symbols():
-        if name in ORIENTED_SYMBOLS + MOTION_SYMBOLS and "PANDASIM_LIB" in os.environ and not hasattr(L, name):
+    for name, (argtypes, restype, group) in SIGNATURES.items():
+        if group and "PANDASIM_LIB" in os.environ and not hasattr(L, name):
             continue  # only a library named by PANDASIM_LIB may predate them
-        if name == "ps_step_oriented":
-            L.ps_step_oriented.argtypes = [V, V, V, V, V, V, V, V, V, V, I, V, V, V]
-        elif name in ORIENTED_SYMBOLS:
-            getattr(L, name).argtypes = [V, V, V, I64, V]
-        getattr(L, name).restype = getattr(L, name).restype if name in ("ps_destroy", "ps_last_error") else I
-    if hasattr(L, "ps_motion_run"):
-        L.ps_motion_plan_bytes.argtypes, L.ps_motion_plan_bytes.restype = [I64], I64
-        L.ps_plan_move.argtypes = [V, V, V, V, V, V, V]
-        L.ps_plan_grasp.argtypes = [V, V, V, V, V]
-        L.ps_plan_release.argtypes = [V, V, V, V, V, V]
-        L.ps_motion_run.argtypes = [V, V, V, I, V]
+        fn = getattr(L, name)
+        if argtypes is not None:
+            fn.argtypes = argtypes
+        fn.restype = restype
     _lib = L
     return L
 

@@ -1,12 +1,16 @@
 """Build libpandasim.so in-tree with hipcc for gfx950 (no JIT, no torch extension).
 
-The library is linked from parallel hipcc jobs (csrc/ps_env.h): the C ABI and
-small kernels (pandasim.hip), the fused step kernels of each (task, control)
-pair (step_kernels.hip: the one-lane kernel, 12 objects, and the 16/8-lane
-group kernels, 10 objects -- Stack has none), the oriented step's kernels of
-each task at ee control (the same source with -DPS_STEP_ORI=1: 6 + 5 objects),
-the plugin-path substep kernel of each scene (sim_kernels.hip, 4 objects) and
-the motion primitives' kernel of each scene (motion_kernels.hip, 4 objects).
+The library is linked from parallel hipcc jobs (csrc/ps_env.h gathers their
+headers): the C ABI's host side (pandasim.hip, no kernel), the fused step
+kernels of each (task, control) pair (step_kernels.hip: the one-lane kernel,
+12 objects, and the 16/8-lane group kernels, 10 objects -- Stack has none),
+the oriented step's kernels of each task at ee control (the same source with
+-DPS_STEP_ORI=1: 6 + 5 objects), the plugin-path substep kernel of each scene
+(sim_kernels.hip, 4 objects), the motion primitives' kernel of each scene
+(motion_kernels.hip, 4 objects), and the small kernels with the entry points
+that launch them, one object per subject: state init / reset / queries / rng /
+reward / Euler conversion (state_kernels.hip), the motion plans
+(plan_kernels.hip), camera, ray caster and deprojection (render_kernels.hip).
 
 Every object is compiled with the same flags (-O3, no -mllvm scheduler
 options).  Round 3 built the group kernels at -O1 after an -O2/-O3 miscompute
@@ -47,26 +51,36 @@ OBJ_DIR = os.path.join(HERE, "build")
 # allocator spill 590 VGPRs of the step kernel to scratch
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-I", INCLUDE]
 
-TASK_STACK = 4  # include/pandasim.h
+# The sets the units are built over, each once here and once in csrc/ps_ctx.h
+# (PS_FOR_EACH_TASK, PS_FOR_EACH_GROUP_TASK, PS_FOR_EACH_SCENE): the tasks of
+# include/pandasim.h, those with group kernels (not Stack, 4) and the scenes
+# (objects, shape) of the plugin path and the motion primitives.
+TASKS = (0, 1, 2, 3, 4, 5)
+GROUP_TASKS = (0, 1, 2, 3, 5)
+SCENES = ((0, 0), (1, 0), (1, 1), (2, 0))
+CONTROLS = (0, 1)  # ee, joints
 
 # (object name, source, defines and per-unit flags)
 UNITS = ([("pandasim", "pandasim.hip", [])]
          + [(f"step_t{t}_c{c}", "step_kernels.hip", [f"-DPS_STEP_TASK={t}", f"-DPS_STEP_CONTROL={c}"])
-            for t in range(6) for c in range(2)]
+            for t in TASKS for c in CONTROLS]
          + [(f"step_t{t}_c{c}_groups", "step_kernels.hip",
              [f"-DPS_STEP_TASK={t}", f"-DPS_STEP_CONTROL={c}", "-DPS_STEP_GROUPS=1"])
-            for t in range(6) if t != TASK_STACK for c in range(2)]
+            for t in GROUP_TASKS for c in CONTROLS]
          # ps_step_oriented's kernels (ee control only): 6 one-lane + 5 group objects
          + [(f"step_ori_t{t}", "step_kernels.hip", [f"-DPS_STEP_TASK={t}", "-DPS_STEP_CONTROL=0", "-DPS_STEP_ORI=1"])
-            for t in range(6)]
+            for t in TASKS]
          + [(f"step_ori_t{t}_groups", "step_kernels.hip",
              [f"-DPS_STEP_TASK={t}", "-DPS_STEP_CONTROL=0", "-DPS_STEP_ORI=1", "-DPS_STEP_GROUPS=1"])
-            for t in range(6) if t != TASK_STACK]
+            for t in GROUP_TASKS]
          + [(f"sim_{n}_{s}", "sim_kernels.hip", [f"-DPS_SIM_NOBJ={n}", f"-DPS_SIM_SHAPE={s}"])
-            for n, s in ((0, 0), (1, 0), (1, 1), (2, 0))]
+            for n, s in SCENES]
          # ps_motion_run's kernel of each scene (k_motion, ps_motion.h): 4 objects
          + [(f"motion_{n}_{s}", "motion_kernels.hip", [f"-DPS_MOTION_NOBJ={n}", f"-DPS_MOTION_SHAPE={s}"])
-            for n, s in ((0, 0), (1, 0), (1, 1), (2, 0))])
+            for n, s in SCENES]
+         # the small kernels with their entry points, by subject
+         + [("state_kernels", "state_kernels.hip", []), ("plan_kernels", "plan_kernels.hip", []),
+            ("render_kernels", "render_kernels.hip", [])])
 
 # diagnostic variants (never loaded by the product unless PANDASIM_LIB names them)
 VARIANTS = {"": [], "prof": ["-DPS_PROFILE_PHASES"]}

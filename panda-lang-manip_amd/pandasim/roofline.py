@@ -3,7 +3,7 @@ DESIGN.md §7).
 
 The cost of each primitive is counted from the formulas the step kernel
 evaluates (``csrc/ps_physics.h`` and the headers it gathers: kinematics,
-dynamics, collide, solver, substep; ``csrc/pandasim.hip``): an FMA is 2 FLOPs,
+dynamics, collide, solver, substep; ``csrc/ps_task.h``, ``csrc/ps_step.h``): an FMA is 2 FLOPs,
 add/sub/mul 1, div/sqrt/rsqrt/rcp/sin/cos/atan2 1 each; comparisons, min/max,
 selects and moves are not counted, and zero entries of the constant URDF
 origin rotations are counted as if they were not known (the algorithm's

@@ -739,7 +739,7 @@ PLANE_Z = -0.4                      # tasks/*.py: create_plane(z_offset=-0.4)
 
 def euler_from_quaternion(q: torch.Tensor) -> torch.Tensor:
     """getEulerFromQuaternion (Bullet btQuaternion::getEulerZYX convention, as
-    ps_task.h::euler_from_quat) for (..., 4) (x, y, z, w) tensors."""
+    ps_task_rng.h::euler_from_quat) for (..., 4) (x, y, z, w) tensors."""
     x, y, z, w = q.unbind(-1)
     sarg = -2.0 * (x * z - w * y)
     roll = torch.atan2(2.0 * (y * z + w * x), w * w - x * x - y * y + z * z)

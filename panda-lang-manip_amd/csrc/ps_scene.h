@@ -217,6 +217,24 @@ constexpr int LDS_CACHE_OFFSET = LDS_STASH_OFFSET + LDS_STASH_FLOATS;
 constexpr int LDS_CACHE_FLOATS = 10;
 constexpr int LDS_FLOATS = LDS_CACHE_OFFSET + LDS_CACHE_FLOATS;
 static_assert(LDS_FLOATS * 4 * 64 * 4 <= 160 * 1024, "four workgroups per CU");
+// The one-lane kernels of these scenes (G == 1, at most one object) lay the
+// M^-1 J^T rows out in 16-byte chunks, [chunk][lane][4] (MJStore::chunk), so
+// the sweep fetches them with ds_read_b128: a slot's 27 floats padded to 28 =
+// 7 chunks.  Lane l's chunk c is floats [256 c + 4 l, 256 c + 4 l + 4) of the
+// workgroup's LDS, i.e. rows 4 c .. 4 c + 3 of the float-major grid, in other
+// lanes' columns: rows [0, 112).  Their stash follows at row 112 without the
+// split-impulse rows (31 floats: split_of rebuilds them from q, as for Stack),
+// and the contact cache stays where it is.
+constexpr int LDS_CHUNK_FLOATS = 28;
+constexpr int LDS_CHUNKS = LDS_CHUNK_FLOATS / 4;
+constexpr int LDS1_STASH_OFFSET = NR * LDS_CHUNK_FLOATS;
+constexpr int LDS1_STASH_FLOATS = LDS_STASH_FLOATS - 9;
+static_assert(LDS1_STASH_OFFSET + LDS1_STASH_FLOATS <= LDS_CACHE_OFFSET, "the one-lane stash below the contact cache");
+// the one-lane solver of which scenes reads its gripper rows as chunks
+template <int NOBJ, int G>
+constexpr bool chunked_lds() {
+    return G == 1 && NOBJ <= 1;
+}
 // Stack (two cubes) keeps in LDS the gripper rows' J (the slots the other
 // scenes use for M^-1 J^T; the loop forms M^-1 J^T from the M^-1 registers)
 // and both cubes' ground rows (r, rhs: 6 per contact; 1/den is rebuilt from r,
@@ -290,6 +308,8 @@ struct RobotContact {
 
 // per-lane view of the LDS rows: element (slot, row, k) at base[((slot*3 + row)*9 + k) * stride]
 typedef __attribute__((address_space(3))) float lds_float;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
 struct MJStore {
     lds_float *base;
     int stride;
@@ -300,6 +320,34 @@ struct MJStore {
     PS_D lds_float &at(int slot, int row, int k) const { return base[((slot * 3 + row) * 9 + k) * stride]; }
     PS_D lds_float &cache(int k) const { return base[(LDS_CACHE_OFFSET + k) * stride]; }
     PS_D lds_float &stash(int k) const { return base[(LDS_STASH_OFFSET + k) * stride]; }
+    // The chunked mode (chunked_lds: one lane per env, one 64-lane wave per
+    // workgroup, base = the workgroup's LDS + lane).  Chunk c of gripper slot
+    // `slot` is 16 bytes per lane, contiguous over the lanes: a ds_read_b128
+    // whose 16-lane groups each cover the 64 banks once (no conflicts).
+    // A slot's chunks: 0-1 row 0's DoFs 0..7, 2-3 row 1's, 4-5 row 2's (the
+    // pairs VelChange::apply takes, on even registers), 6 the rows' DoF 8
+    // (x, y, z) and a pad.
+    PS_D lds_f32x4 &chunk(int slot, int c) const {
+        return ((lds_f32x4 *)(base + 3 * (int)threadIdx.x))[(slot * LDS_CHUNKS + c) * 64];
+    }
+    // row 0 of a slot (the normal's M^-1 J^T): chunks 0, 1 and 6
+    PS_D void chunk_row(int slot, int, float m[9]) const {
+        const f32x4 a = chunk(slot, 0), b = chunk(slot, 1), z = chunk(slot, 6);
+        m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
+        m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
+        m[8] = z.x;
+    }
+    // rows 1 and 2 (the friction rows'): chunks 2..6
+    PS_D void chunk_rows12(int slot, float m1[9], float m2[9]) const {
+        const f32x4 a = chunk(slot, 2), b = chunk(slot, 3), c = chunk(slot, 4), d = chunk(slot, 5), z = chunk(slot, 6);
+        m1[0] = a.x; m1[1] = a.y; m1[2] = a.z; m1[3] = a.w;
+        m1[4] = b.x; m1[5] = b.y; m1[6] = b.z; m1[7] = b.w;
+        m2[0] = c.x; m2[1] = c.y; m2[2] = c.z; m2[3] = c.w;
+        m2[4] = d.x; m2[5] = d.y; m2[6] = d.z; m2[7] = d.w;
+        m1[8] = z.y;
+        m2[8] = z.z;
+    }
+    PS_D lds_float &stash1(int k) const { return base[(LDS1_STASH_OFFSET + k) * stride]; }
     // Stack: the stash in global memory ([GSTASH_PAIR_OFFSET][stride] floats, this env's column)
     // (wave-uniform base and stride, the lane's byte offset: global_* v_off, s[base])
     float *gst = nullptr;

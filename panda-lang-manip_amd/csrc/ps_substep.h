@@ -84,6 +84,7 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
     static_assert(NOBJ < 2 || SHAPE == SHAPE_BOX, "Stack stacks cubes");
     constexpr int NB = NOBJ > 0 ? NOBJ : 1;  // array extents
     constexpr bool ANISO = SHAPE == SHAPE_CYL;
+    constexpr bool CHUNKED = chunked_lds<NOBJ, G>();  // the gripper rows' M^-1 J^T as 16-byte chunks
     const float dt = (float)PM_TIMESTEP;
     float Mi[45], hb[9];
     Geo geo;
@@ -384,8 +385,21 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
 #pragma unroll
         for (int sl = 0; sl < NR; sl++) {
             RobotContact &c = rc[sl];
+            // Chunked rows (MJStore::chunk) land in other lanes' columns, in rows
+            // [28 sl, 28 sl + 28): below every record still unread (slot s's
+            // record starts at row 52 + 14 s), but slot 2's rows cover its own
+            // record's first rows.  So every lane reads the slot's record before
+            // any lane writes the slot's rows, whichever side of the branch
+            // below the wave runs first (one wave: its LDS accesses keep the
+            // program's order)
+            RobotCand cd0{};
+            if constexpr (CHUNKED) {
+                cd0 = RobotCand::load(lds, sl);
+                __builtin_amdgcn_wave_barrier();
+            }
+            float mjc[LDS_CHUNK_FLOATS] = {};
             if (sl < nr) {
-                const RobotCand cd = RobotCand::load(lds, sl);
+                const RobotCand cd = CHUNKED ? cd0 : RobotCand::load(lds, sl);
                 V3 dirs[3];
                 dirs[0] = cd.n;
                 plane_space(cd.n, dirs[1], dirs[2]);
@@ -411,10 +425,16 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
                         float s = 0.0f;
 #pragma unroll
                         for (int b = 0; b < 9; b++) s += Mi[sidx(a, b)] * c.J[j][b];
-                        lds.at(sl, j, a) = NOBJ == 2 ? c.J[j][a] : s;  // Stack: J (M^-1 J^T rebuilt in the loop)
+                        if constexpr (CHUNKED) mjc[a < 8 ? 8 * j + a : 24 + j] = s;
+                        else lds.at(sl, j, a) = NOBJ == 2 ? c.J[j][a] : s;  // Stack: J (M^-1 J^T rebuilt in the loop)
                         if constexpr (NOBJ == 2)
                             if (j == 0) lds.grip(sl, a) = s;
                         den += c.J[j][a] * s;
+                    }
+                    if constexpr (CHUNKED) {
+                        // the row's DoFs 0..7, 16 bytes at a time (DoF 8 goes with chunk 6)
+                        lds.chunk(sl, 2 * j) = (f32x4){mjc[8 * j], mjc[8 * j + 1], mjc[8 * j + 2], mjc[8 * j + 3]};
+                        lds.chunk(sl, 2 * j + 1) = (f32x4){mjc[8 * j + 4], mjc[8 * j + 5], mjc[8 * j + 6], mjc[8 * j + 7]};
                     }
                     float rel = jrow_dot(c.J[j], v1);
                     c.rn[j] = on_obj ? cross(rB, dj) : mk(0, 0, 0);
@@ -431,6 +451,7 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
                     c.lam[j] = 0.0f;
                     c.rhs[j] = j == 0 ? normal_rhs(cd.dist, rel, c.dinv[0]) : -rel * c.dinv[j];
                 }
+                if constexpr (CHUNKED) lds.chunk(sl, 6) = (f32x4){mjc[24], mjc[25], mjc[26], 0.0f};
                 c.lam[0] = warm * cache_lookup(prl, prid, (unsigned)cd.id);
                 nrid |= (unsigned)cd.id << (5 * sl);
             } else {
@@ -442,10 +463,15 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
 #pragma unroll
                     for (int a = 0; a < 9; a++) {
                         c.J[j][a] = 0.0f;
-                        lds.at(sl, j, a) = 0.0f;  // (Stack's grip rows: MJStore::grip_rows reads the zero block)
+                        if constexpr (!CHUNKED)
+                            lds.at(sl, j, a) = 0.0f;  // (Stack's grip rows: MJStore::grip_rows reads the zero block)
                     }
                     c.dir[j] = c.rn[j] = mk(0, 0, 0);
                     c.rhs[j] = c.lam[j] = c.dinv[j] = 0.0f;
+                }
+                if constexpr (CHUNKED) {
+#pragma unroll
+                    for (int k = 0; k < LDS_CHUNKS; k++) lds.chunk(sl, k) = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
                 }
             }
         }
@@ -455,22 +481,26 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
     __builtin_amdgcn_sched_barrier(0);
     // per-substep values the solver never reads wait outside the registers:
     // in LDS, or (Stack, whose LDS holds its ground rows) in the global stash
-    // (Stack: its global stash has no split-impulse rows, 18..26: split_of
-    // rebuilds them from q after the solve, and the rows above shift down)
-    auto gk = [](int k) { return NOBJ == 2 && k >= 27 ? k - 9 : k; };
+    // (Stack's global stash and the chunked layout's LDS stash have no
+    // split-impulse rows, 18..26: split_of rebuilds them from q after the
+    // solve, and the rows above shift down)
+    constexpr bool SPLIT_REBUILT = NOBJ == 2 || CHUNKED;
+    auto gk = [](int k) { return SPLIT_REBUILT && k >= 27 ? k - 9 : k; };
     auto put = [&](int k, float v) {
         if constexpr (NOBJ == 2) lds.gstash(gk(k)) = v;
+        else if constexpr (CHUNKED) lds.stash1(gk(k)) = v;
         else lds.stash(k) = v;
     };
     auto get = [&](const MJStore &S, int k) -> float {
         if constexpr (NOBJ == 2) return S.gstash(gk(k));
+        else if constexpr (CHUNKED) return S.stash1(gk(k));
         else return S.stash(k);
     };
 #pragma unroll
     for (int d = 0; d < 9; d++) {
         put(d, q[d]);
         put(9 + d, v1[d]);
-        if constexpr (NOBJ != 2) put(18 + d, split_dq[d]);
+        if constexpr (!SPLIT_REBUILT) put(18 + d, split_dq[d]);
     }
     if constexpr (NOBJ > 0) {
         put(27, cw1[0].x); put(28, cw1[0].y); put(29, cw1[0].z);
@@ -652,8 +682,11 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
                         mi_apply(g);
                     } else {
                         float w[9];
+                        if constexpr (CHUNKED) W.chunk_row(c, 0, w);
+                        else {
 #pragma unroll
-                        for (int a = 0; a < 9; a++) w[a] = W.at(c, 0, a);
+                            for (int a = 0; a < 9; a++) w[a] = W.at(c, 0, a);
+                        }
 #pragma unroll
                         for (int a = 0; a < 9; a++) dvv.s(a, fmaf(w[a], l0, dvv.g(a)));
                     }
@@ -775,7 +808,9 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
                     float mj[9], Jl[9];
 #pragma unroll
                     for (int a = 0; a < 9; a++) Jl[a] = NOBJ == 2 ? (float)L.at(c, 0, a) : r.J[0][a];
-                    if constexpr (NOBJ != 2) {
+                    if constexpr (CHUNKED) {
+                        L.chunk_row(c, 0, mj);  // three ds_read_b128
+                    } else if constexpr (NOBJ != 2) {
 #pragma unroll
                         for (int a = 0; a < 9; a++) mj[a] = L.at(c, 0, a);
                     }
@@ -924,7 +959,9 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
                         J1[a] = NOBJ == 2 ? (float)L.at(c, 1, a) : r.J[1][a];
                         J2[a] = NOBJ == 2 ? (float)L.at(c, 2, a) : r.J[2][a];
                     }
-                    if constexpr (NOBJ != 2) {
+                    if constexpr (CHUNKED) {
+                        L.chunk_rows12(c, mj1, mj2);  // five ds_read_b128
+                    } else if constexpr (NOBJ != 2) {
 #pragma unroll
                         for (int a = 0; a < 9; a++) {
                             mj1[a] = L.at(c, 1, a);
@@ -1144,7 +1181,7 @@ PS_D void substep(const Scene &sc, float q[9], float qd[9], const Motors &mt, Bo
         for (int d = 0; d < 9; d++) {
             q[d] = get(S, d);
             v1[d] = get(S, 9 + d);
-            split_dq[d] = NOBJ == 2 ? split_of(d, q[d]) : get(S, 18 + d);
+            split_dq[d] = SPLIT_REBUILT ? split_of(d, q[d]) : get(S, 18 + d);
         }
         if constexpr (NOBJ > 0) {
             cw1[0] = mk(get(S, 27), get(S, 28), get(S, 29));

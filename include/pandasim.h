@@ -397,6 +397,57 @@ int ps_deproject_image(ps_ctx *ctx, const float *depth, const double tran_pix_wo
 int ps_deproject_pixels(ps_ctx *ctx, const float *depth, const int32_t *pixels, int n,
                         const double tran_pix_world[16], int width, int height, double *points, void *stream);
 
+/* --- fused multi-view point-cloud observation --- */
+
+/* One view of the observation: what ps_camera returns for it. */
+typedef struct {
+    float view[16], proj[16];
+    double tran_pix_world[16];
+} ps_cloud_view;
+
+/* An extra open box lo < p < hi on the world point (the reference's
+ * filter_outliers; lo z just above the table top drops the table). */
+typedef struct {
+    float lo[3], hi[3];
+} ps_cloud_crop;
+
+/* Bytes of the device workspace of ps_point_cloud: per env and (view, tile of
+ * 256 pixels) 32 B of validity bits, a 4 B count and a 4 B prefix; it does not
+ * grow with n_points.  Host arithmetic only.  PS_ERR_ARG (negative) for
+ * num_envs outside 1..PS_MAX_ENVS, n_views outside 1..8, an empty image, more
+ * than 65 535 pixel tiles or n_views * width * height >= 2^31. */
+int64_t ps_cloud_workspace_bytes(int64_t num_envs, int n_views, int width, int height);
+
+/* The observation the reference's policies start from (grasp.py:122-137,
+ * generate_dset.py:148-195, 334): render n_views views, keep the points
+ * render() keeps, merge, crop, draw n_points with replacement -- in one call,
+ * without the per-pixel arrays.
+ *
+ * The merged cloud of env b is, view 0 first and in row-major pixel order
+ * inside a view, every pixel that ps_deproject_image of that view's ps_render
+ * depth marks valid and whose world point lies strictly inside crop (NULL =
+ * no crop); M_b is its length.  Sample j of env b takes the merged cloud's
+ * entry of rank (z * M_b) >> 64, z the splitmix64 output of counter
+ * c = b * n_points + j:  z = seed + 0x9E3779B97F4A7C15 * (c + 1);
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ * 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64).
+ *
+ * points [B, n_points, 3] f32: ps_deproject_image's f64 world point rounded
+ * once; colors [B, n_points, 3] u8: ps_render's rgb of the pixel; source
+ * [B, n_points] i32: view * width * height + pixel; count [B] i32: M_b.
+ * colors, source and count may be NULL.  An env with M_b = 0 gets points 0,
+ * colors 0 and source -1.  views and crop are HOST memory, the outputs,
+ * targets (as ps_render's) and workspace (ps_cloud_workspace_bytes) device
+ * memory.  Every value is bit-identical to the composition of ps_render and
+ * ps_deproject_image of the same library.
+ * PS_ERR_ARG: a NULL ctx, state, views, vis, points or workspace, n_views
+ * outside 1..8, n_points < 1 (or above 65 535 * 256), an empty image, more
+ * than 65 535 pixel tiles, n_views * width * height >= 2^31. */
+int ps_point_cloud(ps_ctx *ctx, const void *state, const ps_cloud_view *views, int n_views, int width, int height,
+                   const ps_visual *vis, const float *targets, const ps_cloud_crop *crop, int n_points,
+                   uint64_t seed, float *points, uint8_t *colors, int32_t *source, int32_t *count, void *workspace,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

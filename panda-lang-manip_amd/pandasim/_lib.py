@@ -44,6 +44,16 @@ class Visual(C.Structure):
     _fields_ = [("rgba", (C.c_float * 4) * 8), ("target_shape", C.c_int32 * 2), ("target_half", (C.c_float * 3) * 2)]
 
 
+class CloudView(C.Structure):
+    """ps_cloud_view: one view of ps_point_cloud, as ps_camera returns it."""
+    _fields_ = [("view", C.c_float * 16), ("proj", C.c_float * 16), ("tran_pix_world", C.c_double * 16)]
+
+
+class CloudCrop(C.Structure):
+    """ps_cloud_crop: the open box lo < p < hi on the world point."""
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
 VISUAL_SPHERE = 2
 ROLES = ("plane", "table", "object1", "object2", "target1", "target2", "robot", "background")
 
@@ -69,7 +79,8 @@ F, D = P(C.c_float), P(C.c_double)
 # added within ABI version 6: a library built before them (one of the two that
 # scripts/compare_libs.py loads under PANDASIM_LIB) still binds, and calling
 # one on it raises AttributeError -- "oriented" the oriented step, "motion" the
-# motion primitives (panda_cartesian.py move / grasp / release).
+# motion primitives (panda_cartesian.py move / grasp / release), "cloud" the
+# fused point-cloud observation (PandaSim.point_cloud).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -109,9 +120,13 @@ SIGNATURES = {
     "ps_plan_grasp": ([V, V, V, V, V], I, "motion"),
     "ps_plan_release": ([V, V, V, V, V, V], I, "motion"),
     "ps_motion_run": ([V, V, V, I, V], I, "motion"),
+    "ps_cloud_workspace_bytes": ([I64, I, I, I], I64, "cloud"),
+    "ps_point_cloud": ([V, V, V, I, I, I, P(Visual), V, V, I, C.c_uint64, V, V, V, V, V, V], I, "cloud"),
 }
 ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
 MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
+CLOUD_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "cloud")
+CLOUD_MAX_VIEWS = 8
 
 
 def exported_symbols():

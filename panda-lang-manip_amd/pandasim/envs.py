@@ -211,6 +211,12 @@ class PandaVecEnv:
         view, proj, _ = self.sim.get_cam2world_transforms(width, height, target_position, distance, yaw, pitch, roll)
         return self.sim.get_camera_image(width, height, view, proj)[1]
 
+    def point_cloud(self, views=None, n_points: int = 5000, width: int = 480, height: int = 480, seed: int = 0,
+                    crop=None):
+        """The fused multi-view point-cloud observation of every env
+        (PandaSim.point_cloud): points [B, K, 3], colors, source, count."""
+        return self.sim.point_cloud(views, n_points, width, height, seed, crop)
+
     def close(self) -> None:
         self.sim.close()
 

@@ -24,6 +24,8 @@ CONTROLS = {"ee": 0, "joints": 1}
 REWARDS = {"sparse": 0, "dense": 1}
 JOINT_TO_DOF = {0: 0, 1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 6, 9: 7, 10: 8}
 DT_SUBSTEP = 1.0 / 500
+# the four views around the table that the grasp task merges (task_classes/grasp.py:129-132)
+GRASP_VIEWS = tuple(dict(distance=0.6, target_position=[0, 0, 0.1], yaw=yaw) for yaw in (0, 135, 245, 300))
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -426,6 +428,53 @@ class PandaSim:
         return (out["rgb"][env].cpu().numpy(), out["depth"][env].double().cpu().numpy(),
                 out["points"][env].cpu().numpy()[keep], out["colors"][env].cpu().numpy()[keep],
                 out["pixels_2d"][env].cpu().numpy()[keep], waypoints_proj)
+
+    def point_cloud(self, views=None, n_points: int = 5000, width: int = 480, height: int = 480, seed: int = 0,
+                    crop=None) -> Dict[str, torch.Tensor]:
+        """The policies' observation (grasp.py:122-137, generate_dset.py:148-195,
+        334): render() from every view, np.vstack of the filtered point
+        clouds, an optional crop, np.random.choice(len(points), n_points) --
+        fused (ps_point_cloud), for every env, without the per-pixel arrays.
+
+        views: a list of dicts of get_cam2world_transforms' keyword arguments
+        (default GRASP_VIEWS); crop: ((lo x, y, z), (hi x, y, z)), an extra
+        open box on the world point.  Returns points [B, K, 3] f32, colors
+        [B, K, 3] u8 (render()'s colors), source [B, K] i32 (view * width *
+        height + pixel of each sample) and count [B] i32 (the merged cloud's
+        size; an env with none gets points 0, colors 0, source -1).  The draw
+        is a counter-based splitmix64 of `seed`: the same seed repeats it."""
+        self._check_image_size(width, height)
+        views = GRASP_VIEWS if views is None else list(views)
+        if not 1 <= len(views) <= L.CLOUD_MAX_VIEWS:
+            raise ValueError(f"point_cloud: {len(views)} views (1 to {L.CLOUD_MAX_VIEWS})")
+        if n_points < 1:
+            raise ValueError("point_cloud: n_points < 1")
+        B, K = self.num_envs, int(n_points)
+        cv = (L.CloudView * len(views))()
+        for v, kw in zip(cv, views):
+            view, proj, tran = self.get_cam2world_transforms(width, height, **kw)
+            v.view[:], v.proj[:], v.tran_pix_world[:] = view, proj, tran.reshape(-1).tolist()
+        box = None
+        if crop is not None:
+            box = L.CloudCrop()
+            box.lo[:], box.hi[:] = [float(x) for x in crop[0]], [float(x) for x in crop[1]]
+        nbytes = self._lib.ps_cloud_workspace_bytes(B, len(views), int(width), int(height))
+        if nbytes < 0:
+            raise ValueError(f"point_cloud: {len(views)} views of {width}x{height} are more than one call takes")
+        ws = getattr(self, "_cloud_ws", None)
+        if ws is None or ws.numel() != nbytes:  # cached by size
+            ws = self._cloud_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = {"points": torch.empty(B, K, 3, dtype=torch.float32, device=self.device),
+               "colors": torch.empty(B, K, 3, dtype=torch.uint8, device=self.device),
+               "source": torch.empty(B, K, dtype=torch.int32, device=self.device),
+               "count": torch.empty(B, dtype=torch.int32, device=self.device)}
+        vis = self._visual()
+        targets = self._target_poses().contiguous()
+        self._call("ps_point_cloud", self._ctx, _ptr(self.state), cv, len(views), int(width), int(height),
+                   C.byref(vis), _ptr(targets), None if box is None else C.byref(box), K,
+                   int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out["points"]), _ptr(out["colors"]), _ptr(out["source"]),
+                   _ptr(out["count"]), _ptr(ws), self._stream())
+        return out
 
     def deproject(self, depth, pixels, tran_pix_world, width: int = 480, height: int = 480) -> torch.Tensor:
         """PyBullet.deproject (pybullet.py:109-146) per env: depth [B, h, w]

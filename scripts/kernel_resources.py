@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Register, scratch and LDS use of every step and motion kernel of a built object or
+"""Register, scratch and LDS use of every step, motion, render and point-cloud kernel of a built object or
 library, from the code objects' AMDGPU metadata (no GPU needed).
 
 usage: python scripts/kernel_resources.py [lib or .o ...] [--json out.json]
@@ -40,17 +40,40 @@ def code_objects(path: str, tmp: str) -> list:
 
 def kernels(co: str) -> dict:
     txt = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
-    res, cur = {}, None
+    # One record per entry of amdhsa.kernels: its keys come sorted, so a kernel's
+    # .agpr_count and .group_segment_fixed_size stand before its .name.  A record
+    # starts at a list item of the kernels' own indent (their .args sit deeper).
+    res, rec, indent, inside = {}, None, None, False
+
+    def close(r):
+        if r and "k_" in r.get("name", ""):
+            res[r.pop("name")] = r
+
     for line in txt.splitlines():
-        m = re.match(r"\s*-?\s*\.name:\s+(\S+)", line)
-        if m and "k_" in m.group(1):
-            cur = m.group(1)
-            res[cur] = {}
+        if "amdhsa.kernels:" in line:
+            inside, indent = True, None
             continue
+        if not inside:
+            continue
+        m = re.match(r"(\s*)- \.", line)
+        if m and (indent is None or len(m.group(1)) == indent):
+            indent = len(m.group(1))
+            close(rec)
+            rec = {}
+        elif re.match(r"\s{0,%d}\S" % (indent or 0), line) and not m:
+            close(rec)  # left the kernels list
+            rec, inside = None, False
+            continue
+        if rec is None or (len(line) - len(line.lstrip())) > (indent or 0) + 2:
+            continue  # a key of an argument
+        m = re.match(r"\s*(?:- )?\.name:\s+(\S+)", line)
+        if m:
+            rec["name"] = m.group(1)
         for f in FIELDS:
-            m = re.match(r"\s*" + re.escape(f) + r":\s+(\d+)", line)
-            if m and cur:
-                res[cur][f[1:]] = int(m.group(1))
+            m = re.match(r"\s*(?:- )?" + re.escape(f) + r":\s+(\d+)", line)
+            if m:
+                rec[f[1:]] = int(m.group(1))
+    close(rec)
     return res
 
 
@@ -68,13 +91,15 @@ def main(argv):
     paths = argv or sorted(glob.glob(os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim",
                                                   "step_*.o")) +
                           glob.glob(os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim",
-                                                 "motion_*.o")))
+                                                 "motion_*.o")) +
+                          [os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim", n)
+                           for n in ("render_kernels.o", "cloud_kernels.o")])
     table = {}
     with tempfile.TemporaryDirectory() as tmp:
         for p in paths:
             for co in code_objects(p, tmp):
                 for k, v in kernels(co).items():
-                    if "k_step" in k or "k_sim_step" in k or "k_motion" in k:
+                    if any(n in k for n in ("k_step", "k_sim_step", "k_motion", "k_render", "k_deproject", "k_cloud")):
                         table[demangle(k)] = v
     for k, v in sorted(table.items()):
         print(f"{k:40s} vgpr {v.get('vgpr_count', 0):3d} agpr {v.get('agpr_count', 0):3d} "

@@ -448,6 +448,81 @@ int ps_point_cloud(ps_ctx *ctx, const void *state, const ps_cloud_view *views, i
                    uint64_t seed, float *points, uint8_t *colors, int32_t *source, int32_t *count, void *workspace,
                    void *stream);
 
+/* --- PointNet++ front end of the point-cloud observation --- */
+
+/* What the reference's policies do to every cloud before a learned weight is
+ * touched (envs/inference/models/pointnet2_utils.py): pc_normalize,
+ * farthest_point_sample, query_ball_point, and the index_points gathers with
+ * the centring of PointNetSetAbstractionMsg.forward.  Every call works on the
+ * context's B = num_envs clouds of N points; all pointers are device memory
+ * unless said otherwise, every call is ordered on `stream`.
+ *
+ * The squared distance of two points is, everywhere below,
+ *   d = a - b;  d2 = (d.x * d.x + d.y * d.y) + d.z * d.z
+ * in f32 with every product and sum rounded (no fused multiply-add).
+ *
+ * Limits (PS_ERR_ARG, nothing launched, outputs untouched): a NULL required
+ * pointer, N outside 1..PS_CLOUD_MAX_POINTS, S outside 1..N, nsample < 1, a
+ * radius that is not positive and finite, D outside 0..PS_CLOUD_MAX_FEATURES
+ * or D != 0 without feats (and the reverse), n_scales outside
+ * 1..PS_CLOUD_MAX_SCALES.  Indices read from device memory (start, centre_idx,
+ * group_idx) cannot be refused by a stream-ordered call: a value outside
+ * 0..N-1 is clamped into it, so nothing is read out of bounds; the Python
+ * layer refuses such a start before the call. */
+#define PS_CLOUD_MAX_POINTS 8192  /* 12 B of LDS per point in one workgroup */
+#define PS_CLOUD_MAX_SCALES 4
+#define PS_CLOUD_MAX_FEATURES 16
+
+/* pc_normalize of points [B, N, 3]: centroid [B, 3] = the mean of the N rows,
+ * accumulated in f64 in a fixed order (partial sum t of 256 takes rows t,
+ * t + 256, ...; the partials are added by halving) and rounded once to f32;
+ * scale [B] = the largest sqrt(d2(p, centroid)); xyz_out [B, N, 3] =
+ * (p - centroid) / scale.  A cloud of scale 0 yields zeros, not NaN. */
+int ps_cloud_normalize(ps_ctx *ctx, const float *points, int N, float *xyz_out, float *centroid, float *scale,
+                       void *stream);
+
+/* farthest_point_sample of xyz [B, N, 3] from start [B] i32 (the reference
+ * draws it) into idx [B, S] i32:  dist = 1e10 for every point, far = start;
+ * S times: emit far; dist = min(dist, d2(x, x[far])); far = the arg-max of
+ * dist, the lowest index among equal values. */
+int ps_cloud_fps(ps_ctx *ctx, const float *xyz, int N, const int32_t *start, int S, int32_t *idx, void *stream);
+
+/* query_ball_point: group_idx [B, S, nsample] i32 = per centre
+ * xyz[centre_idx[b, s]] the first nsample indices, in ascending order, whose
+ * d2 to the centre is not > (float)(radius * radius) (the product in f64, as
+ * the reference compares with radius ** 2); fewer than nsample are padded with
+ * the first.  No sort and no distance matrix. */
+int ps_cloud_ball_query(ps_ctx *ctx, const float *xyz, int N, const int32_t *centre_idx, int S, double radius,
+                        int nsample, int32_t *group_idx, void *stream);
+
+/* The gathers and the centring, in the layout and channel order of
+ * PointNetSetAbstractionMsg.forward before its permute:
+ * out [B, S, nsample, D + 3] = feats[group_idx] (feats [B, N, D] f32, NULL
+ * with D = 0) followed by xyz[group_idx] - xyz[centre_idx];
+ * new_xyz [B, S, 3] = xyz[centre_idx], may be NULL. */
+int ps_cloud_group(ps_ctx *ctx, const float *xyz, const float *feats, int N, int D, const int32_t *centre_idx, int S,
+                   const int32_t *group_idx, int nsample, float *out, float *new_xyz, void *stream);
+
+/* One radius of ps_cloud_set_abstraction: group_idx [B, S, nsample] i32 and
+ * grouped [B, S, nsample, D + 3] f32 (may be NULL: indices only). */
+typedef struct {
+    double radius;
+    int32_t nsample;
+    int32_t *group_idx;
+    float *grouped;
+} ps_cloud_scale;
+
+/* The first set-abstraction layer's sampling and grouping in one call:
+ * normalise (if `normalize`: xyz, centroid, scale as ps_cloud_normalize; else
+ * the cloud is `points` itself and the three may be NULL), ps_cloud_fps into
+ * fps_idx [B, S], then for each of n_scales scales (HOST array) the ball query
+ * around the sampled points and the group, the scales sharing one walk over
+ * the points; new_xyz [B, S, 3] may be NULL.  Every value equals the
+ * composition of the four calls above bit for bit.  No workspace. */
+int ps_cloud_set_abstraction(ps_ctx *ctx, const float *points, const float *feats, int N, int D, const int32_t *start,
+                             int S, const ps_cloud_scale *scales, int n_scales, int normalize, float *xyz,
+                             float *centroid, float *scale, int32_t *fps_idx, float *new_xyz, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

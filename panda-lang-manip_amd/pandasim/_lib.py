@@ -49,6 +49,11 @@ class CloudView(C.Structure):
     _fields_ = [("view", C.c_float * 16), ("proj", C.c_float * 16), ("tran_pix_world", C.c_double * 16)]
 
 
+class CloudScale(C.Structure):
+    """ps_cloud_scale: one radius of ps_cloud_set_abstraction (device pointers)."""
+    _fields_ = [("radius", C.c_double), ("nsample", C.c_int32), ("group_idx", C.c_void_p), ("grouped", C.c_void_p)]
+
+
 class CloudCrop(C.Structure):
     """ps_cloud_crop: the open box lo < p < hi on the world point."""
     _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
@@ -80,7 +85,8 @@ F, D = P(C.c_float), P(C.c_double)
 # scripts/compare_libs.py loads under PANDASIM_LIB) still binds, and calling
 # one on it raises AttributeError -- "oriented" the oriented step, "motion" the
 # motion primitives (panda_cartesian.py move / grasp / release), "cloud" the
-# fused point-cloud observation (PandaSim.point_cloud).
+# fused point-cloud observation (PandaSim.point_cloud), "group" the PointNet++
+# front end of that observation (PandaSim.group_cloud).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -122,11 +128,18 @@ SIGNATURES = {
     "ps_motion_run": ([V, V, V, I, V], I, "motion"),
     "ps_cloud_workspace_bytes": ([I64, I, I, I], I64, "cloud"),
     "ps_point_cloud": ([V, V, V, I, I, I, P(Visual), V, V, I, C.c_uint64, V, V, V, V, V, V], I, "cloud"),
+    "ps_cloud_normalize": ([V, V, I, V, V, V, V], I, "group"),
+    "ps_cloud_fps": ([V, V, I, V, I, V, V], I, "group"),
+    "ps_cloud_ball_query": ([V, V, I, V, I, C.c_double, I, V, V], I, "group"),
+    "ps_cloud_group": ([V, V, V, I, I, V, I, V, I, V, V, V], I, "group"),
+    "ps_cloud_set_abstraction": ([V, V, V, I, I, V, I, P(CloudScale), I, I, V, V, V, V, V, V], I, "group"),
 }
 ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
 MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
 CLOUD_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "cloud")
+GROUP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "group")
 CLOUD_MAX_VIEWS = 8
+CLOUD_MAX_POINTS, CLOUD_MAX_SCALES, CLOUD_MAX_FEATURES = 8192, 4, 16
 
 
 def exported_symbols():

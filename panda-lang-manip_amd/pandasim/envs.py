@@ -217,6 +217,13 @@ class PandaVecEnv:
         (PandaSim.point_cloud): points [B, K, 3], colors, source, count."""
         return self.sim.point_cloud(views, n_points, width, height, seed, crop)
 
+    def group_cloud(self, points, feats=None, npoint: int = 512, radii=(0.1, 0.2, 0.4), nsamples=(32, 64, 128),
+                    seed: int = 0, normalize: bool = True, start=None):
+        """The PointNet++ front end on point_cloud()'s tensors
+        (PandaSim.group_cloud): normalise, farthest point sampling, ball query
+        and grouping of every env's cloud."""
+        return self.sim.group_cloud(points, feats, npoint, radii, nsamples, seed, normalize, start)
+
     def close(self) -> None:
         self.sim.close()
 

@@ -476,6 +476,48 @@ class PandaSim:
                    _ptr(out["count"]), _ptr(ws), self._stream())
         return out
 
+    def group_cloud(self, points, feats=None, npoint: int = 512, radii=(0.1, 0.2, 0.4), nsamples=(32, 64, 128),
+                    seed: int = 0, normalize: bool = True, start=None) -> "GroupedCloud":
+        """What the reference's policies do to every cloud before the first
+        learned weight (pointnet2_utils.py: pc_normalize, farthest_point_sample,
+        query_ball_point, index_points and the centring of
+        PointNetSetAbstractionMsg.forward) -- fused (ps_cloud_set_abstraction),
+        for every env, without the distance matrix and the sort.  The defaults
+        are model_cls_off_rot.py's first layer.
+
+        points [B, N, 3] f32 (point_cloud()'s "points"), feats None or
+        [B, N, D] f32 with D <= 16 (its "colors" as .float()).  The first
+        sampled point of env b is start[b] (i32 [B], each in [0, N)) or, with
+        start None, fps_start(seed, b, N): the point cloud's splitmix64 draw of
+        counter b, so a seed repeats.  Returns a GroupedCloud."""
+        B = self.num_envs
+        pts = torch.as_tensor(points, device=self.device)
+        if feats is not None:
+            feats = torch.as_tensor(feats, device=self.device)
+        N, S, D, radii, nsamples, first = group_cloud_args(B, pts, feats, npoint, radii, nsamples, seed, start)
+        feats = None if feats is None else feats.contiguous()
+        first = first.to(self.device)
+        pts = pts.contiguous()
+        dev = self.device
+        out = GroupedCloud()
+        if normalize:
+            out.xyz = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+            out.centroid = torch.empty(B, 3, dtype=torch.float32, device=dev)
+            out.scale = torch.empty(B, dtype=torch.float32, device=dev)
+        else:
+            out.xyz, out.centroid, out.scale = pts, None, None
+        out.fps_idx = torch.empty(B, S, dtype=torch.int32, device=dev)
+        out.new_xyz = torch.empty(B, S, 3, dtype=torch.float32, device=dev)
+        out.group_idx = [torch.empty(B, S, k, dtype=torch.int32, device=dev) for k in nsamples]
+        out.grouped = [torch.empty(B, S, k, D + 3, dtype=torch.float32, device=dev) for k in nsamples]
+        scales = (L.CloudScale * len(radii))()
+        for sc, r, k, gi, g in zip(scales, radii, nsamples, out.group_idx, out.grouped):
+            sc.radius, sc.nsample, sc.group_idx, sc.grouped = r, k, gi.data_ptr(), g.data_ptr()
+        self._call("ps_cloud_set_abstraction", self._ctx, _ptr(pts), _ptr(feats), N, D, _ptr(first), S, scales,
+                   len(radii), int(bool(normalize)), _ptr(out.xyz) if normalize else None, _ptr(out.centroid),
+                   _ptr(out.scale), _ptr(out.fps_idx), _ptr(out.new_xyz), self._stream())
+        return out
+
     def deproject(self, depth, pixels, tran_pix_world, width: int = 480, height: int = 480) -> torch.Tensor:
         """PyBullet.deproject (pybullet.py:109-146) per env: depth [B, h, w]
         (or one [h, w] image for every env), pixels [n, 2] or [B, n, 2]
@@ -760,6 +802,64 @@ class PandaSim:
     def motion_run(self, plan: "MotionPlan", max_steps: int) -> None:
         """ps_motion_run: every env runs min(max_steps, num_steps - done) control steps."""
         self._call("ps_motion_run", self._ctx, _ptr(self.state), _ptr(plan.buf), int(max_steps), self._stream())
+
+
+class GroupedCloud:
+    """PandaSim.group_cloud's result: xyz [B, N, 3] (normalised; the input
+    itself with normalize=False), centroid [B, 3] and scale [B] (None with
+    normalize=False), fps_idx [B, S] i32, new_xyz [B, S, 3], and per scale
+    group_idx[k] [B, S, nsample_k] i32 and grouped[k] [B, S, nsample_k, D + 3]
+    (the features, then the centred coordinates)."""
+
+    __slots__ = ("xyz", "centroid", "scale", "fps_idx", "new_xyz", "group_idx", "grouped")
+
+
+def fps_start(seed: int, env: int, n: int) -> int:
+    """The point farthest point sampling starts from in env `env`'s cloud of n
+    points under `seed`: (z * n) >> 64, z the splitmix64 output of counter
+    `env` (include/pandasim.h, ps_point_cloud's draw)."""
+    m = (1 << 64) - 1
+    z = ((int(seed) & m) + 0x9E3779B97F4A7C15 * (env + 1)) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return ((z ^ (z >> 31)) * int(n)) >> 64
+
+
+def group_cloud_args(num_envs: int, points, feats, npoint, radii, nsamples, seed, start):
+    """group_cloud's argument checks (ValueError), on tensors of any device:
+    -> N, S, D, radii, nsamples and the start indices (i32 [B], on the CPU)."""
+    B = int(num_envs)
+    if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"group_cloud: points must be [{B}, N, 3] float32, got {tuple(points.shape)} {points.dtype}")
+    N, S = int(points.shape[1]), int(npoint)
+    if not 1 <= N <= L.CLOUD_MAX_POINTS:
+        raise ValueError(f"group_cloud: N = {N} points (1 to {L.CLOUD_MAX_POINTS})")
+    if not 1 <= S <= N:
+        raise ValueError(f"group_cloud: npoint = {S} (1 to N = {N})")
+    radii, nsamples = [float(r) for r in radii], [int(k) for k in nsamples]
+    if len(radii) != len(nsamples) or not 1 <= len(radii) <= L.CLOUD_MAX_SCALES:
+        raise ValueError(f"group_cloud: {len(radii)} radii and {len(nsamples)} nsamples (equal, 1 to "
+                         f"{L.CLOUD_MAX_SCALES})")
+    if any(not (0.0 < r < math.inf) for r in radii) or any(k < 1 for k in nsamples):
+        raise ValueError("group_cloud: a radius must be positive and finite, an nsample at least 1")
+    D = 0
+    if feats is not None:
+        if feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N) or feats.dtype != torch.float32:
+            raise ValueError(f"group_cloud: feats must be [{B}, {N}, D] float32, got {tuple(feats.shape)} "
+                             f"{feats.dtype}")
+        D = int(feats.shape[2])
+        if not 1 <= D <= L.CLOUD_MAX_FEATURES:
+            raise ValueError(f"group_cloud: D = {D} feature channels (1 to {L.CLOUD_MAX_FEATURES})")
+    if start is None:
+        first = torch.tensor([fps_start(seed, b, N) for b in range(B)], dtype=torch.int32)
+    else:
+        first = torch.as_tensor(start).detach().cpu().reshape(-1)
+        if first.numel() != B or first.is_floating_point() or first.dtype == torch.bool:
+            raise ValueError(f"group_cloud: start must be {B} integers")
+        if int(first.min()) < 0 or int(first.max()) >= N:
+            raise ValueError(f"group_cloud: start outside [0, {N})")
+        first = first.to(torch.int32)
+    return N, S, D, radii, nsamples, first
 
 
 class MotionPlan:

@@ -523,6 +523,58 @@ int ps_cloud_set_abstraction(ps_ctx *ctx, const float *points, const float *feat
                              int S, const ps_cloud_scale *scales, int n_scales, int normalize, float *xyz,
                              float *centroid, float *scale, int32_t *fps_idx, float *new_xyz, void *stream);
 
+/* --- PointNet++ feature propagation: 3-NN interpolation --- */
+
+/* The interpolation inside PointNetFeaturePropagation.forward
+ * (pointnet2_utils.py:276-310), the step between the learned layers of every
+ * segmentation and keypoint model (fp3, fp2, fp1), for the context's B clouds:
+ * xyz1 [B, N, 3] f32 the dense points, xyz2 [B, S, 3] f32 the coarse points,
+ * points2 [B, S, D2] f32 the coarse features, points1 [B, N, D1] f32 the dense
+ * features (NULL with D1 = 0).  No distance matrix and no sort.
+ *
+ * Per dense point n, in f32 with every product, sum and quotient rounded (no
+ * fused multiply-add, correctly rounded division):
+ *   d2_j      = the squared distance above of xyz1[n] and xyz2[j], every j;
+ *   i_0..i_2  = the three smallest d2 in ascending order, the lowest index
+ *               first among equal values;
+ *   w_k       = 1.0f / (d2_k + 1e-8f);   norm = (w_0 + w_1) + w_2;
+ *   weight_k  = w_k / norm;
+ *   interp[c] = (points2[i_0][c] * weight_0 + points2[i_1][c] * weight_1)
+ *               + points2[i_2][c] * weight_2.
+ * S = 1 is the reference's repeat: idx = (0, 0, 0), weight = (1, 0, 0) and
+ * interp = points2[b, 0] itself.  S = 2 is refused, as the reference raises
+ * there.  The three indices of a cloud whose distances are all finite are
+ * distinct; a distance that is not finite never displaces an index, so every
+ * index written is inside 0..S-1 whatever the input.
+ *
+ * Limits (PS_ERR_ARG, nothing launched, outputs untouched): a NULL required
+ * pointer, N outside 1..PS_CLOUD_MAX_DENSE_POINTS, S outside
+ * 1..PS_CLOUD_MAX_POINTS or S = 2, D2 outside 1..PS_CLOUD_MAX_PROP_FEATURES,
+ * D1 outside 0..PS_CLOUD_MAX_PROP_FEATURES, D1 != 0 without points1 (and the
+ * reverse).  Outputs are addressed with 64-bit offsets. */
+#define PS_CLOUD_MAX_PROP_FEATURES 2048
+#define PS_CLOUD_MAX_DENSE_POINTS 1048576 /* 2^20 */
+
+/* idx [B, N, 3] i32 and weight [B, N, 3] f32 of every dense point. */
+int ps_cloud_three_nn(ps_ctx *ctx, const float *xyz1, int N, const float *xyz2, int S, int32_t *idx, float *weight,
+                      void *stream);
+
+/* out [B, N, D1 + D2] = points1 followed by interp, from idx and weight as
+ * ps_cloud_three_nn writes them: the layout and channel order of forward
+ * before its final permute.  An idx read from device memory is clamped into
+ * 0..S-1, as the group entry points clamp theirs.  With S = 1 idx and weight
+ * are not read. */
+int ps_cloud_interpolate(ps_ctx *ctx, const float *points1, int D1, const float *points2, int D2, int N, int S,
+                         const int32_t *idx, const float *weight, float *out, void *stream);
+
+/* Both in one launch: a workgroup finds the 3-NN of its dense points, keeps
+ * idx and weight on chip and writes those points' rows of out.  idx and
+ * weight may be NULL (not written).  Every value equals the composition of
+ * the two calls above bit for bit.  No workspace. */
+int ps_cloud_feature_propagation(ps_ctx *ctx, const float *xyz1, int N, const float *xyz2, int S,
+                                 const float *points1, int D1, const float *points2, int D2, float *out,
+                                 int32_t *idx, float *weight, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@
 // The squared distance is (dx*dx + dy*dy) + dz*dz with every product and sum
 // rounded to f32 (dist2): the form that reproduces the reference's FPS index
 // for index; an FMA or another tie-break gives other indices.
-#include "ps_ctx.h"
+#include "ps_cloud_math.h"
 
 namespace {
 
@@ -35,21 +35,8 @@ constexpr int kGatherBlock = 256;
 constexpr int kGatherMaxBlocks = 1024;  // per (cloud, scale); the rest by a grid stride
 static_assert(kFpsPer * kFpsBlock == kGroupMaxN && kFpsPer == 8, "a lane owns at most 8 points");
 
-// an opaque copy: hipcc contracts a*b+c across inlined calls even under
-// `fp contract(off)` (ps_task_rng.h); a product that went through here stays a
-// rounded value of its own
-PS_D float rounded(float x) {
-    asm("" : "+v"(x));
-    return x;
-}
-
-PS_D float dist2(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (rounded(dx * dx) + rounded(dy * dy)) + rounded(dz * dz);
-}
-
-PS_D int clamp_index(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+// rounded(), dist2() and clamp_index() are ps_cloud_math.h's, shared with
+// propagate_kernels.hip
 
 // ------------------------------------------------------------- normalise
 // The mean's order: lane t of 256 adds rows t, t + 256, ... in f64, the 256

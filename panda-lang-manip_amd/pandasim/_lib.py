@@ -86,7 +86,8 @@ F, D = P(C.c_float), P(C.c_double)
 # one on it raises AttributeError -- "oriented" the oriented step, "motion" the
 # motion primitives (panda_cartesian.py move / grasp / release), "cloud" the
 # fused point-cloud observation (PandaSim.point_cloud), "group" the PointNet++
-# front end of that observation (PandaSim.group_cloud).
+# front end of that observation (PandaSim.group_cloud), "propagate" its
+# feature propagation (PandaSim.propagate_features).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -133,13 +134,18 @@ SIGNATURES = {
     "ps_cloud_ball_query": ([V, V, I, V, I, C.c_double, I, V, V], I, "group"),
     "ps_cloud_group": ([V, V, V, I, I, V, I, V, I, V, V, V], I, "group"),
     "ps_cloud_set_abstraction": ([V, V, V, I, I, V, I, P(CloudScale), I, I, V, V, V, V, V, V], I, "group"),
+    "ps_cloud_three_nn": ([V, V, I, V, I, V, V, V], I, "propagate"),
+    "ps_cloud_interpolate": ([V, V, I, V, I, I, I, V, V, V, V], I, "propagate"),
+    "ps_cloud_feature_propagation": ([V, V, I, V, I, V, I, V, I, V, V, V, V], I, "propagate"),
 }
 ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
 MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
 CLOUD_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "cloud")
 GROUP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "group")
+PROPAGATE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "propagate")
 CLOUD_MAX_VIEWS = 8
 CLOUD_MAX_POINTS, CLOUD_MAX_SCALES, CLOUD_MAX_FEATURES = 8192, 4, 16
+CLOUD_MAX_PROP_FEATURES, CLOUD_MAX_DENSE_POINTS = 2048, 1 << 20
 
 
 def exported_symbols():

@@ -224,6 +224,12 @@ class PandaVecEnv:
         and grouping of every env's cloud."""
         return self.sim.group_cloud(points, feats, npoint, radii, nsamples, seed, normalize, start)
 
+    def propagate_features(self, xyz1, xyz2, points2, points1=None, return_nn: bool = False):
+        """PointNet++ feature propagation of every env's cloud
+        (PandaSim.propagate_features): 3-NN interpolation of the coarse
+        features onto the dense points, behind the dense points' own."""
+        return self.sim.propagate_features(xyz1, xyz2, points2, points1, return_nn)
+
     def close(self) -> None:
         self.sim.close()
 

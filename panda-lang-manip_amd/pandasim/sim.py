@@ -518,6 +518,33 @@ class PandaSim:
                    _ptr(out.scale), _ptr(out.fps_idx), _ptr(out.new_xyz), self._stream())
         return out
 
+    def propagate_features(self, xyz1, xyz2, points2, points1=None, return_nn: bool = False):
+        """The interpolation of PointNetFeaturePropagation.forward
+        (pointnet2_utils.py:276-310) -- fused (ps_cloud_feature_propagation),
+        for every env, without the distance matrix and the sort: each dense
+        point's three nearest coarse points, inverse-distance weights, the
+        weighted sum of their features behind the dense point's own.
+
+        xyz1 [B, N, 3] f32 the dense points, xyz2 [B, S, 3] f32 the coarse
+        points (S = 1 or S >= 3), points2 [B, S, D2] f32 their features,
+        points1 None or [B, N, D1] f32; D1, D2 <= 2048.  Returns out
+        [B, N, D1 + D2] f32 (points1, then the interpolation: forward's tensor
+        before its final permute), with return_nn also idx [B, N, 3] i32 and
+        weight [B, N, 3] f32."""
+        B, dev = self.num_envs, self.device
+        xyz1, xyz2, points2 = (torch.as_tensor(t, device=dev) for t in (xyz1, xyz2, points2))
+        if points1 is not None:
+            points1 = torch.as_tensor(points1, device=dev)
+        N, S, D1, D2 = propagate_features_args(B, xyz1, xyz2, points2, points1)
+        xyz1, xyz2, points2 = xyz1.contiguous(), xyz2.contiguous(), points2.contiguous()
+        points1 = None if points1 is None else points1.contiguous()
+        out = torch.empty(B, N, D1 + D2, dtype=torch.float32, device=dev)
+        idx = torch.empty(B, N, 3, dtype=torch.int32, device=dev) if return_nn else None
+        weight = torch.empty(B, N, 3, dtype=torch.float32, device=dev) if return_nn else None
+        self._call("ps_cloud_feature_propagation", self._ctx, _ptr(xyz1), N, _ptr(xyz2), S, _ptr(points1), D1,
+                   _ptr(points2), D2, _ptr(out), _ptr(idx), _ptr(weight), self._stream())
+        return (out, idx, weight) if return_nn else out
+
     def deproject(self, depth, pixels, tran_pix_world, width: int = 480, height: int = 480) -> torch.Tensor:
         """PyBullet.deproject (pybullet.py:109-146) per env: depth [B, h, w]
         (or one [h, w] image for every env), pixels [n, 2] or [B, n, 2]
@@ -860,6 +887,35 @@ def group_cloud_args(num_envs: int, points, feats, npoint, radii, nsamples, seed
             raise ValueError(f"group_cloud: start outside [0, {N})")
         first = first.to(torch.int32)
     return N, S, D, radii, nsamples, first
+
+
+def propagate_features_args(num_envs: int, xyz1, xyz2, points2, points1):
+    """propagate_features' argument checks (ValueError), on tensors of any
+    device: -> N, S, D1, D2."""
+    B = int(num_envs)
+    for name, t in (("xyz1", xyz1), ("xyz2", xyz2)):
+        if t.dim() != 3 or t.shape[0] != B or t.shape[2] != 3 or t.dtype != torch.float32:
+            raise ValueError(f"propagate_features: {name} must be [{B}, points, 3] float32, got {tuple(t.shape)} "
+                             f"{t.dtype}")
+    N, S = int(xyz1.shape[1]), int(xyz2.shape[1])
+    if not 1 <= N <= L.CLOUD_MAX_DENSE_POINTS:
+        raise ValueError(f"propagate_features: N = {N} dense points (1 to {L.CLOUD_MAX_DENSE_POINTS})")
+    if not 1 <= S <= L.CLOUD_MAX_POINTS or S == 2:
+        raise ValueError(f"propagate_features: S = {S} coarse points (1, or 3 to {L.CLOUD_MAX_POINTS}: the "
+                         f"reference's interpolation takes three neighbours and raises on two)")
+    if points2.dim() != 3 or tuple(points2.shape[:2]) != (B, S) or points2.dtype != torch.float32:
+        raise ValueError(f"propagate_features: points2 must be [{B}, {S}, D2] float32, got {tuple(points2.shape)} "
+                         f"{points2.dtype}")
+    D1, D2 = 0, int(points2.shape[2])
+    if points1 is not None:
+        if points1.dim() != 3 or tuple(points1.shape[:2]) != (B, N) or points1.dtype != torch.float32:
+            raise ValueError(f"propagate_features: points1 must be [{B}, {N}, D1] float32, got "
+                             f"{tuple(points1.shape)} {points1.dtype}")
+        D1 = int(points1.shape[2])
+    if not 1 <= D2 <= L.CLOUD_MAX_PROP_FEATURES or (points1 is not None and not 1 <= D1 <= L.CLOUD_MAX_PROP_FEATURES):
+        raise ValueError(f"propagate_features: D1 = {D1}, D2 = {D2} feature channels (1 to "
+                         f"{L.CLOUD_MAX_PROP_FEATURES} each; no points1 for none)")
+    return N, S, D1, D2
 
 
 class MotionPlan:

@@ -575,6 +575,70 @@ int ps_cloud_feature_propagation(ps_ctx *ctx, const float *xyz1, int N, const fl
                                  const float *points1, int D1, const float *points2, int D2, float *out,
                                  int32_t *idx, float *weight, void *stream);
 
+/* --- PointNet++ shared MLP with max-pool, on the f32 matrix cores --- */
+
+/* What every model of envs/inference/models/ does to the tensors above: the
+ * loop F.relu(bn(conv(x))) over 1x1 convolutions followed by torch.max over
+ * the neighbourhood (pointnet2_utils.py:196-200 and :253-257), the same loop
+ * without the max (:312-314), and the head's conv1 / conv2 -- at inference,
+ * with the batch norm folded into the weights by the caller
+ * (pandasim.fold_batchnorm).  Weights, checkpoints, training, dropout and
+ * log_softmax are not part of the library.
+ *
+ * A layer is W [c_out, c_in] f32 row-major (a conv weight with its trailing 1s
+ * dropped), b [c_out] f32, and a relu flag; W and b are device memory, shared
+ * by all clouds; the array of layers is HOST memory.  c_in of the first layer
+ * is C0, of every other the c_out before it.
+ *
+ * Per row x [C0] and layer, in f32:
+ *   y[o] = b[o];  for k = 0 .. c_in-1 ascending:  y[o] = fmaf(x[k], W[o][k], y[o]);
+ *   if relu:  y[o] = y[o] > 0 ? y[o] : 0;
+ * the next layer reads y.  One rounding per step, nothing wider in between:
+ * the f32-input MFMA of gfx950 computes exactly this chain from its C operand,
+ * so the accumulators start as the bias and k is never split.
+ * With group size G, output row g is the element-wise maximum over rows
+ * g G .. g G + G - 1 of the last layer's y; G = 1 is no pooling.
+ * Comparisons are by value (-0 equals +0: which zero is written is
+ * unspecified).  The result for an input, weight or bias that is not finite
+ * is unspecified.
+ *
+ * Limits (PS_ERR_ARG, nothing launched, outputs untouched): a NULL required
+ * pointer (a layer's W or b included), n_layers outside
+ * 1..PS_CLOUD_MLP_MAX_LAYERS, C0 outside 1..PS_CLOUD_MAX_PROP_FEATURES + 3, a
+ * c_out outside 1..PS_CLOUD_MLP_MAX_HIDDEN (the last layer's:
+ * 1..PS_CLOUD_MLP_MAX_LAST), R < 1, G < 1, R not a multiple of G, out_offset
+ * < 0, out_stride < out_offset + the last c_out.  Outputs are addressed with
+ * 64-bit offsets. */
+#define PS_CLOUD_MLP_MAX_LAYERS 4
+#define PS_CLOUD_MLP_MAX_HIDDEN 512 /* a 32-row tile's two live activations stay in LDS */
+#define PS_CLOUD_MLP_MAX_LAST 1024
+
+typedef struct {
+    const float *W; /* [c_out, c_in] */
+    const float *b; /* [c_out] */
+    int32_t c_out;
+    int32_t relu;
+} ps_cloud_mlp_layer;
+
+/* rows [B, R, C0] f32 -> out[b, g, out_offset + c] for g in 0..R/G-1 and c in
+ * 0..C_n-1 (C_n the last c_out); the pitch of an out row is out_stride floats,
+ * columns outside out_offset .. out_offset + C_n - 1 are not written. */
+int ps_cloud_mlp(ps_ctx *ctx, const float *rows, int R, int C0, const ps_cloud_mlp_layer *layers, int n_layers, int G,
+                 float *out, int64_t out_stride, int out_offset, void *stream);
+
+/* The same on the rows of ps_cloud_group, gathered inside the kernel (the
+ * grouped tensor never exists): row (s, k) is feats[group_idx[b, s, k]]
+ * followed by xyz[group_idx[b, s, k]] - xyz[centre_idx[b, s]] (the subtraction
+ * in f32, as there), so C0 = D + 3, R = S * K and G = K:
+ * out[b, s, out_offset + c].  N and S as ps_cloud_group's, D in
+ * 0..PS_CLOUD_MAX_PROP_FEATURES (feats NULL with D = 0), K >= 1; indices are
+ * clamped as there.  Every value equals ps_cloud_group followed by
+ * ps_cloud_mlp bit for bit.  The column offset is how the scales of
+ * PointNetSetAbstractionMsg land in one [B, S, sum C_n] tensor. */
+int ps_cloud_group_mlp(ps_ctx *ctx, const float *xyz, const float *feats, int N, int D, const int32_t *centre_idx,
+                       int S, const int32_t *group_idx, int K, const ps_cloud_mlp_layer *layers, int n_layers,
+                       float *out, int64_t out_stride, int out_offset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

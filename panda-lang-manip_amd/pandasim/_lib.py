@@ -54,6 +54,11 @@ class CloudScale(C.Structure):
     _fields_ = [("radius", C.c_double), ("nsample", C.c_int32), ("group_idx", C.c_void_p), ("grouped", C.c_void_p)]
 
 
+class CloudMlpLayer(C.Structure):
+    """ps_cloud_mlp_layer: W [c_out, c_in] and b [c_out] (device pointers)."""
+    _fields_ = [("W", C.c_void_p), ("b", C.c_void_p), ("c_out", C.c_int32), ("relu", C.c_int32)]
+
+
 class CloudCrop(C.Structure):
     """ps_cloud_crop: the open box lo < p < hi on the world point."""
     _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
@@ -87,7 +92,8 @@ F, D = P(C.c_float), P(C.c_double)
 # motion primitives (panda_cartesian.py move / grasp / release), "cloud" the
 # fused point-cloud observation (PandaSim.point_cloud), "group" the PointNet++
 # front end of that observation (PandaSim.group_cloud), "propagate" its
-# feature propagation (PandaSim.propagate_features).
+# feature propagation (PandaSim.propagate_features), "mlp" the shared MLP with
+# max-pool (PandaSim.shared_mlp / abstract_features).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -137,15 +143,19 @@ SIGNATURES = {
     "ps_cloud_three_nn": ([V, V, I, V, I, V, V, V], I, "propagate"),
     "ps_cloud_interpolate": ([V, V, I, V, I, I, I, V, V, V, V], I, "propagate"),
     "ps_cloud_feature_propagation": ([V, V, I, V, I, V, I, V, I, V, V, V, V], I, "propagate"),
+    "ps_cloud_mlp": ([V, V, I, I, P(CloudMlpLayer), I, I, V, I64, I, V], I, "mlp"),
+    "ps_cloud_group_mlp": ([V, V, V, I, I, V, I, V, I, P(CloudMlpLayer), I, V, I64, I, V], I, "mlp"),
 }
 ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
 MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
 CLOUD_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "cloud")
 GROUP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "group")
 PROPAGATE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "propagate")
+MLP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "mlp")
 CLOUD_MAX_VIEWS = 8
 CLOUD_MAX_POINTS, CLOUD_MAX_SCALES, CLOUD_MAX_FEATURES = 8192, 4, 16
 CLOUD_MAX_PROP_FEATURES, CLOUD_MAX_DENSE_POINTS = 2048, 1 << 20
+CLOUD_MLP_MAX_LAYERS, CLOUD_MLP_MAX_HIDDEN, CLOUD_MLP_MAX_LAST = 4, 512, 1024
 
 
 def exported_symbols():

@@ -230,6 +230,16 @@ class PandaVecEnv:
         features onto the dense points, behind the dense points' own."""
         return self.sim.propagate_features(xyz1, xyz2, points2, points1, return_nn)
 
+    def shared_mlp(self, rows, layers, pool: int = 1, out=None, out_offset: int = 0):
+        """The shared MLP with max-pool of every env's rows
+        (PandaSim.shared_mlp)."""
+        return self.sim.shared_mlp(rows, layers, pool, out, out_offset)
+
+    def abstract_features(self, xyz, feats=None, centre_idx=None, group_idx=None, mlps=None, fused=None):
+        """The learned half of a multi-scale set abstraction of every env's
+        cloud (PandaSim.abstract_features)."""
+        return self.sim.abstract_features(xyz, feats, centre_idx, group_idx, mlps, fused)
+
     def close(self) -> None:
         self.sim.close()
 

@@ -4,12 +4,13 @@ Host layer over libpandasim.so (HIP, gfx950).  See DESIGN.md.
 """
 from . import panda_cartesian
 from ._lib import PandasimError, lib
+from .cloudnet import CloudMlp, fold_batchnorm
 from .core import PyBulletRobot, RobotTaskEnv, Task, TimeLimit
 from .envs import REGISTRY, PandaVecEnv, make
 from .panda_tasks import (PandaFlipEnv, PandaPickAndPlaceEnv, PandaPushEnv, PandaReachEnv, PandaSlideEnv,
                           PandaStackEnv)
 from .robots import Panda
-from .sim import GRASP_VIEWS, CloudMlp, PandaSim, fold_batchnorm
+from .sim import GRASP_VIEWS, PandaSim
 from .tasks import Flip, PickAndPlace, Push, Reach, Slide, Stack
 
 __all__ = ["make", "PandaVecEnv", "PandaSim", "GRASP_VIEWS", "CloudMlp", "fold_batchnorm", "REGISTRY", "PandasimError", "lib", "PyBulletRobot",

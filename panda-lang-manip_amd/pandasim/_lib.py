@@ -235,3 +235,8 @@ def default_config(task: int, control: int, reward: int) -> Config:
     cfg = Config()
     check(lib().ps_default_config(task, control, reward, C.byref(cfg)), what="ps_default_config")
     return cfg
+
+
+def _ptr(t):
+    """A tensor's address as a void-pointer argument; None stays NULL."""
+    return None if t is None else C.c_void_p(t.data_ptr())

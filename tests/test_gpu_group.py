@@ -3,53 +3,38 @@ _ball_query / _group / _set_abstraction, PandaSim.group_cloud).
 
 Two yardsticks, both exact: the golden recorded from the reference's
 pointnet2_utils.py (tests/golden/group_golden.npz; ball-query rows marked
-ambiguous there are skipped, and only those) and tests/test_group_cpu.py's
+ambiguous there are skipped, and only those) and tests/cloud_reference.py's
 numpy restatement run on the same inputs, which uses the kernels' own
 comparison and excuses no row.  Only the normalisation has a tolerance:
 2 * eps_f32 * max|value| against an f64 pc_normalize of the same f32 input (one
 f32 rounding of the centroid, one subtraction, one division).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from test_group_cpu import (CASES, QUERY_CASES, assert_matches_golden, ball_query_np, case_of, fps_np, group_np,
-                            normalize_np, restated)
+from cloud_helpers import DEV, dev, make_sims, raw_call, raw_group, same_bits
+from cloud_reference import ball_query_np, fps_np, group_rows_np, normalize_np
+from test_group_cpu import CASES, QUERY_CASES, assert_matches_golden, case_of, restated
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 EPS = float(np.finfo(np.float32).eps)
 
 
 @pytest.fixture(scope="module")
 def sims():
     """Contexts of 3 clouds (the golden's batch) and of 1."""
-    from pandasim.sim import PandaSim
-
-    return {n: PandaSim("reach", num_envs=n, device=DEV) for n in (3, 1)}
-
-
-def dev(a, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
+    return make_sims((3, 1))
 
 
 # ------------------------------------------------ the raw calls (ctypes)
-def _rc(sim, name, *args):
-    from pandasim import _lib as L
-
-    with torch.cuda.device(sim.device):
-        return getattr(L.lib(), name)(*args)
-
-
 def raw_normalize(sim, pts, check=True):
     from pandasim.sim import _ptr
 
     nb, n = pts.shape[:2]
     out = (torch.empty(nb, n, 3, device=DEV), torch.empty(nb, 3, device=DEV), torch.empty(nb, device=DEV))
-    rc = _rc(sim, "ps_cloud_normalize", sim._ctx, _ptr(pts), n, *(_ptr(t) for t in out), sim._stream())
+    rc = raw_call(sim, "ps_cloud_normalize", sim._ctx, _ptr(pts), n, *(_ptr(t) for t in out), sim._stream())
     assert not check or rc == 0
     return out
 
@@ -58,7 +43,7 @@ def raw_fps(sim, xyz, start, s):
     from pandasim.sim import _ptr
 
     idx = torch.empty(xyz.shape[0], s, dtype=torch.int32, device=DEV)
-    assert _rc(sim, "ps_cloud_fps", sim._ctx, _ptr(xyz), xyz.shape[1], _ptr(start), s, _ptr(idx), sim._stream()) == 0
+    assert raw_call(sim, "ps_cloud_fps", sim._ctx, _ptr(xyz), xyz.shape[1], _ptr(start), s, _ptr(idx), sim._stream()) == 0
     return idx
 
 
@@ -67,28 +52,9 @@ def raw_query(sim, xyz, centre_idx, radius, nsample):
 
     nb, s = centre_idx.shape
     gidx = torch.empty(nb, s, nsample, dtype=torch.int32, device=DEV)
-    assert _rc(sim, "ps_cloud_ball_query", sim._ctx, _ptr(xyz), xyz.shape[1], _ptr(centre_idx), s, float(radius),
+    assert raw_call(sim, "ps_cloud_ball_query", sim._ctx, _ptr(xyz), xyz.shape[1], _ptr(centre_idx), s, float(radius),
                nsample, _ptr(gidx), sim._stream()) == 0
     return gidx
-
-
-def raw_group(sim, xyz, feats, centre_idx, gidx):
-    from pandasim.sim import _ptr
-
-    nb, s, nsample = gidx.shape
-    d = 0 if feats is None else feats.shape[2]
-    out = torch.empty(nb, s, nsample, d + 3, device=DEV)
-    new_xyz = torch.empty(nb, s, 3, device=DEV)
-    assert _rc(sim, "ps_cloud_group", sim._ctx, _ptr(xyz), _ptr(feats), xyz.shape[1], d, _ptr(centre_idx), s,
-               _ptr(gidx), nsample, _ptr(out), _ptr(new_xyz), sim._stream()) == 0
-    return out, new_xyz
-
-
-def same_bits(a, b):
-    a, b = a.cpu().numpy(), b.cpu().numpy()
-    if a.dtype == np.float32:
-        a, b = a.view(np.uint32), b.view(np.uint32)
-    return a.shape == b.shape and np.array_equal(a, b)
 
 
 # -------------------------------------------------------------------- FPS
@@ -119,7 +85,7 @@ def test_ball_query_and_group_equal_the_golden_and_the_restatement(sims, name):
     xyz, feats, cidx = dev(c["xyz"]), dev(c["feats"]), dev(c["fps_idx"])
     for k, (radius, nsample) in enumerate(c["scales"]):
         gidx = raw_query(sims[3], xyz, cidx, radius, nsample)
-        grouped, new_xyz = raw_group(sims[3], xyz, feats, cidx, gidx)
+        grouped, new_xyz = raw_group(sims[3], xyz, feats, cidx, gidx, new_xyz=True)
         g, gr = gidx.cpu().numpy(), grouped.cpu().numpy()
         assert_matches_golden(name, k, g, gr, "kernels")
         # every row, against the restatement (the golden's centres are its own: test_group_cpu)
@@ -128,7 +94,7 @@ def test_ball_query_and_group_equal_the_golden_and_the_restatement(sims, name):
         want_new = np.stack([c["xyz"][b][c["fps_idx"][b]] for b in range(3)])
         assert np.array_equal(new_xyz.cpu().numpy(), want_new)
         # without features: the centred coordinates alone
-        bare, _ = raw_group(sims[3], xyz, None, cidx, gidx)
+        bare, _ = raw_group(sims[3], xyz, None, cidx, gidx, new_xyz=True)
         assert np.array_equal(bare.cpu().numpy().view(np.uint32), r[f"grouped_{k}"][..., 4:].view(np.uint32))
 
 
@@ -193,7 +159,7 @@ def test_fused_equals_the_four_calls_composed(sims, name, with_feats, normalize)
         assert np.array_equal(idx.cpu().numpy(), c["fps_idx"])
     for k, (radius, nsample) in enumerate(c["scales"]):
         gidx = raw_query(sim, xyz, idx, radius, nsample)
-        grouped, new_xyz = raw_group(sim, xyz, feats, idx, gidx)
+        grouped, new_xyz = raw_group(sim, xyz, feats, idx, gidx, new_xyz=True)
         assert same_bits(got.group_idx[k], gidx), (name, k)
         assert same_bits(got.grouped[k], grouped), (name, k)
         assert same_bits(got.new_xyz, new_xyz)
@@ -220,7 +186,7 @@ def test_a_clouds_result_does_not_depend_on_the_batch(sims):
 
 
 def test_same_seed_repeats_and_the_start_is_the_counter_draw(sims):
-    from pandasim.sim import fps_start
+    from pandasim.cloudnet import fps_start
     from test_cloud_cpu import rank
 
     c = case_of("B")
@@ -252,13 +218,13 @@ def test_point_cloud_into_group_cloud():
     xyz = g.xyz[0].cpu().numpy()
     wx, wc, ws = normalize_np(cloud["points"][0].cpu().numpy())
     assert np.abs(xyz - wx).max() <= 2 * EPS * np.abs(wx).max()
-    from pandasim.sim import fps_start
+    from pandasim.cloudnet import fps_start
 
     idx = fps_np(xyz, fps_start(4, 0, K), 32)
     gidx = ball_query_np(xyz, idx, 0.2, 16)
     assert np.array_equal(g.fps_idx[0].cpu().numpy(), idx)
     assert np.array_equal(g.group_idx[0][0].cpu().numpy(), gidx)
-    want = group_np(xyz, cloud["colors"][0].float().cpu().numpy(), idx, gidx).astype(np.float32)
+    want = group_rows_np(xyz[None], cloud["colors"].float().cpu().numpy(), idx[None], gidx[None])[0]
     assert np.array_equal(g.grouped[0][0].cpu().numpy().view(np.uint32), want.view(np.uint32))
     assert np.array_equal(g.new_xyz[0].cpu().numpy(), xyz[idx])
     got = g.group_idx[0][0].cpu().numpy()
@@ -288,7 +254,7 @@ def test_argument_errors_leave_the_outputs_untouched(sims):
 
     def fused(points=xyz, f=feats, n_=n, d=4, s_=s, scales=scale, n_scales=1, normalize=1, x=o3, fidx=idx,
               start_=start, context=ctx):
-        return _rc(sim, "ps_cloud_set_abstraction", context, p(points), p(f), n_, d, p(start_), s_, scales, n_scales,
+        return raw_call(sim, "ps_cloud_set_abstraction", context, p(points), p(f), n_, d, p(start_), s_, scales, n_scales,
                    normalize, p(x), p(cen), p(sc), p(fidx), p(nx), st)
 
     def with_scale(radius, nsample, group_idx=gidx):
@@ -298,30 +264,30 @@ def test_argument_errors_leave_the_outputs_untouched(sims):
         return bad
 
     codes = [
-        _rc(sim, "ps_cloud_normalize", None, p(xyz), n, p(o3), p(cen), p(sc), st),
-        _rc(sim, "ps_cloud_normalize", ctx, None, n, p(o3), p(cen), p(sc), st),
-        _rc(sim, "ps_cloud_normalize", ctx, p(xyz), n, None, p(cen), p(sc), st),
-        _rc(sim, "ps_cloud_normalize", ctx, p(xyz), 0, p(o3), p(cen), p(sc), st),
-        _rc(sim, "ps_cloud_normalize", ctx, p(xyz), 8193, p(o3), p(cen), p(sc), st),
-        _rc(sim, "ps_cloud_fps", ctx, p(xyz), n, p(start), 0, p(idx), st),  # S < 1
-        _rc(sim, "ps_cloud_fps", ctx, p(xyz), n, p(start), n + 1, p(idx), st),  # S > N
-        _rc(sim, "ps_cloud_fps", ctx, p(xyz), 8193, p(start), s, p(idx), st),
-        _rc(sim, "ps_cloud_fps", ctx, p(xyz), 0, p(start), 0, p(idx), st),
-        _rc(sim, "ps_cloud_fps", ctx, p(xyz), n, None, s, p(idx), st),
-        _rc(sim, "ps_cloud_fps", ctx, p(xyz), n, p(start), s, None, st),
+        raw_call(sim, "ps_cloud_normalize", None, p(xyz), n, p(o3), p(cen), p(sc), st),
+        raw_call(sim, "ps_cloud_normalize", ctx, None, n, p(o3), p(cen), p(sc), st),
+        raw_call(sim, "ps_cloud_normalize", ctx, p(xyz), n, None, p(cen), p(sc), st),
+        raw_call(sim, "ps_cloud_normalize", ctx, p(xyz), 0, p(o3), p(cen), p(sc), st),
+        raw_call(sim, "ps_cloud_normalize", ctx, p(xyz), 8193, p(o3), p(cen), p(sc), st),
+        raw_call(sim, "ps_cloud_fps", ctx, p(xyz), n, p(start), 0, p(idx), st),  # S < 1
+        raw_call(sim, "ps_cloud_fps", ctx, p(xyz), n, p(start), n + 1, p(idx), st),  # S > N
+        raw_call(sim, "ps_cloud_fps", ctx, p(xyz), 8193, p(start), s, p(idx), st),
+        raw_call(sim, "ps_cloud_fps", ctx, p(xyz), 0, p(start), 0, p(idx), st),
+        raw_call(sim, "ps_cloud_fps", ctx, p(xyz), n, None, s, p(idx), st),
+        raw_call(sim, "ps_cloud_fps", ctx, p(xyz), n, p(start), s, None, st),
     ]
     for radius, nsample in ((0.0, 16), (-0.2, 16), (inf, 16), (nan, 16), (0.2, 0), (0.2, -3)):
-        codes.append(_rc(sim, "ps_cloud_ball_query", ctx, p(xyz), n, p(cidx), s, radius, nsample, p(gidx), st))
+        codes.append(raw_call(sim, "ps_cloud_ball_query", ctx, p(xyz), n, p(cidx), s, radius, nsample, p(gidx), st))
         codes.append(fused(scales=with_scale(radius, nsample)))
     codes += [
-        _rc(sim, "ps_cloud_ball_query", ctx, p(xyz), n, p(cidx), n + 1, 0.2, 16, p(gidx), st),
-        _rc(sim, "ps_cloud_ball_query", ctx, p(xyz), n, None, s, 0.2, 16, p(gidx), st),
-        _rc(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 17, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
-        _rc(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, -1, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
-        _rc(sim, "ps_cloud_group", ctx, p(xyz), None, n, 4, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
-        _rc(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 0, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
-        _rc(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 4, p(cidx), s, p(gidx), 0, p(out), p(nx), st),
-        _rc(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 4, p(cidx), s, p(gidx), 16, None, p(nx), st),
+        raw_call(sim, "ps_cloud_ball_query", ctx, p(xyz), n, p(cidx), n + 1, 0.2, 16, p(gidx), st),
+        raw_call(sim, "ps_cloud_ball_query", ctx, p(xyz), n, None, s, 0.2, 16, p(gidx), st),
+        raw_call(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 17, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
+        raw_call(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, -1, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
+        raw_call(sim, "ps_cloud_group", ctx, p(xyz), None, n, 4, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
+        raw_call(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 0, p(cidx), s, p(gidx), 16, p(out), p(nx), st),
+        raw_call(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 4, p(cidx), s, p(gidx), 0, p(out), p(nx), st),
+        raw_call(sim, "ps_cloud_group", ctx, p(xyz), p(feats), n, 4, p(cidx), s, p(gidx), 16, None, p(nx), st),
         fused(context=None), fused(points=None), fused(start_=None), fused(fidx=None), fused(scales=None),
         fused(x=None), fused(n_=0), fused(n_=8193), fused(s_=0), fused(s_=n + 1), fused(d=17), fused(f=None),
         fused(d=0), fused(n_scales=0), fused(n_scales=5), fused(scales=with_scale(0.2, 16, None)),

@@ -1,7 +1,7 @@
 """GPU tests of the shared MLP with max-pool (ps_cloud_mlp, ps_cloud_group_mlp,
 PandaSim.shared_mlp / abstract_features).
 
-The yardstick is tests/test_mlp_cpu.py's numpy restatement (an exact fmaf chain
+The yardstick is tests/cloud_reference.py's numpy restatement (an exact fmaf chain
 from the bias, k ascending) run on the same inputs; the kernels equal it on
 every element, by value (-0 equals +0).  That restatement is held to the f64
 golden recorded from the reference within a bound derived there; the golden
@@ -12,24 +12,19 @@ import numpy as np
 import pytest
 import torch
 
-from test_mlp_cpu import CASES, case_of, folded, golden, group_rows_np, mlp_np, restated
+from cloud_helpers import DEV, dev, make_sims, raw_call, raw_group
+from cloud_reference import group_rows_np, mlp_np
+from test_mlp_cpu import CASES, case_of, folded, golden, restated
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SENTINEL = -12345.5
 
 
 @pytest.fixture(scope="module")
 def sims():
     """Contexts of 2 clouds (the golden's batch), of 1 and of 7."""
-    from pandasim.sim import PandaSim
-
-    return {n: PandaSim("reach", num_envs=n, device=DEV) for n in (2, 1, 7)}
-
-
-def dev(a, dtype=None):
-    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
+    return make_sims((2, 1, 7))
 
 
 def same_values(got, want):
@@ -56,13 +51,6 @@ def upload(layers):
     return CloudMlp(layers, DEV)
 
 
-def _rc(sim, name, *args):
-    from pandasim import _lib as L
-
-    with torch.cuda.device(sim.device):
-        return getattr(L.lib(), name)(*args)
-
-
 def raw_mlp(sim, rows, mlp, pool=1, out=None, offset=0, expect=0):
     """ps_cloud_mlp on a device tensor rows [B, R, C0]; -> out."""
     from pandasim.sim import _ptr
@@ -70,19 +58,8 @@ def raw_mlp(sim, rows, mlp, pool=1, out=None, offset=0, expect=0):
     nb, r, c0 = rows.shape
     if out is None:
         out = torch.full((nb, r // pool, mlp.widths[-1]), SENTINEL, device=DEV)
-    assert _rc(sim, "ps_cloud_mlp", sim._ctx, _ptr(rows), r, c0, mlp.array, len(mlp), pool, _ptr(out), out.shape[2],
+    assert raw_call(sim, "ps_cloud_mlp", sim._ctx, _ptr(rows), r, c0, mlp.array, len(mlp), pool, _ptr(out), out.shape[2],
                offset, sim._stream()) == expect
-    return out
-
-
-def raw_group(sim, xyz, feats, centre_idx, gidx):
-    from pandasim.sim import _ptr
-
-    nb, n = xyz.shape[:2]
-    d, (s, k) = 0 if feats is None else feats.shape[2], gidx.shape[1:]
-    out = torch.empty(nb, s, k, d + 3, device=DEV)
-    assert _rc(sim, "ps_cloud_group", sim._ctx, _ptr(xyz), _ptr(feats), n, d, _ptr(centre_idx), s, _ptr(gidx), k,
-               _ptr(out), None, sim._stream()) == 0
     return out
 
 
@@ -93,7 +70,7 @@ def raw_group_mlp(sim, xyz, feats, centre_idx, gidx, mlp, out=None, offset=0, ex
     d, (s, k) = 0 if feats is None else feats.shape[2], gidx.shape[1:]
     if out is None:
         out = torch.full((nb, s, mlp.widths[-1]), SENTINEL, device=DEV)
-    assert _rc(sim, "ps_cloud_group_mlp", sim._ctx, _ptr(xyz), _ptr(feats), n, d, _ptr(centre_idx), s, _ptr(gidx), k,
+    assert raw_call(sim, "ps_cloud_group_mlp", sim._ctx, _ptr(xyz), _ptr(feats), n, d, _ptr(centre_idx), s, _ptr(gidx), k,
                mlp.array, len(mlp), _ptr(out), out.shape[2], offset, sim._stream()) == expect
     return out
 
@@ -305,11 +282,11 @@ def test_every_refusal_leaves_the_outputs_untouched(sims):
         return a
 
     def mlp(*, ctx=sim._ctx, rows=rows, R=16, C0=9, layers=array(32, 64), n=2, G=1, out=out, stride=64, offset=0):
-        return _rc(sim, "ps_cloud_mlp", ctx, _ptr(rows), R, C0, layers, n, G, _ptr(out), stride, offset, sim._stream())
+        return raw_call(sim, "ps_cloud_mlp", ctx, _ptr(rows), R, C0, layers, n, G, _ptr(out), stride, offset, sim._stream())
 
     def gmlp(*, xyz=xyz, feats=feats, N=40, D=6, centre=centre, S=4, gidx=gidx, K=4, layers=array(32, 64), n=2,
              out=out, stride=64, offset=0):
-        return _rc(sim, "ps_cloud_group_mlp", sim._ctx, _ptr(xyz), _ptr(feats), N, D, _ptr(centre), S, _ptr(gidx), K,
+        return raw_call(sim, "ps_cloud_group_mlp", sim._ctx, _ptr(xyz), _ptr(feats), N, D, _ptr(centre), S, _ptr(gidx), K,
                    layers, n, _ptr(out), stride, offset, sim._stream())
 
     bad_mlp = [dict(ctx=None), dict(rows=None), dict(layers=None), dict(out=None), dict(n=0), dict(n=5, layers=array(8, 8, 8, 8, 8)),

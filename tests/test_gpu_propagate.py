@@ -1,7 +1,7 @@
 """GPU tests of the PointNet++ feature propagation (ps_cloud_three_nn /
 _interpolate / _feature_propagation, PandaSim.propagate_features).
 
-The yardstick is tests/test_propagate_cpu.py's numpy restatement run on the
+The yardstick is tests/cloud_reference.py's numpy restatement run on the
 same inputs, which the kernels equal bit for bit on every row: idx index for
 index, weight and out bit for bit.  That restatement is held to the f64 golden
 recorded from the reference within 12 eps_f32 max|points2| there, so the
@@ -12,50 +12,27 @@ import numpy as np
 import pytest
 import torch
 
-from test_propagate_cpu import CASES, EPS, K_BOUND, SHAPES, case_of, propagate_np, restated
+from cloud_helpers import DEV, dev, make_sims, raw_call, same_bits
+from cloud_reference import propagate_np
+from test_propagate_cpu import CASES, EPS, K_BOUND, SHAPES, case_of, restated
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
 def sims():
     """Contexts of 2 clouds (the golden's batch), of 1 and of 7."""
-    from pandasim.sim import PandaSim
-
-    return {n: PandaSim("reach", num_envs=n, device=DEV) for n in (2, 1, 7)}
-
-
-def dev(a, dtype=None):
-    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
-
-
-def bits(t):
-    a = t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same_bits(a, b):
-    a, b = bits(a), bits(b)
-    return a.shape == b.shape and np.array_equal(a, b)
+    return make_sims((2, 1, 7))
 
 
 # ------------------------------------------------ the raw calls (ctypes)
-def _rc(sim, name, *args):
-    from pandasim import _lib as L
-
-    with torch.cuda.device(sim.device):
-        return getattr(L.lib(), name)(*args)
-
-
 def raw_three_nn(sim, xyz1, xyz2):
     from pandasim.sim import _ptr
 
     nb, n = xyz1.shape[:2]
     idx = torch.empty(nb, n, 3, dtype=torch.int32, device=DEV)
     weight = torch.empty(nb, n, 3, device=DEV)
-    assert _rc(sim, "ps_cloud_three_nn", sim._ctx, _ptr(xyz1), n, _ptr(xyz2), xyz2.shape[1], _ptr(idx), _ptr(weight),
+    assert raw_call(sim, "ps_cloud_three_nn", sim._ctx, _ptr(xyz1), n, _ptr(xyz2), xyz2.shape[1], _ptr(idx), _ptr(weight),
                sim._stream()) == 0
     return idx, weight
 
@@ -66,7 +43,7 @@ def raw_interpolate(sim, points1, points2, idx, weight):
     nb, n = idx.shape[:2]
     d1, (s, d2) = 0 if points1 is None else points1.shape[2], points2.shape[1:]
     out = torch.empty(nb, n, d1 + d2, device=DEV)
-    assert _rc(sim, "ps_cloud_interpolate", sim._ctx, _ptr(points1), d1, _ptr(points2), d2, n, s, _ptr(idx),
+    assert raw_call(sim, "ps_cloud_interpolate", sim._ctx, _ptr(points1), d1, _ptr(points2), d2, n, s, _ptr(idx),
                _ptr(weight), _ptr(out), sim._stream()) == 0
     return out
 
@@ -79,7 +56,7 @@ def raw_fused(sim, xyz1, xyz2, points2, points1=None, nn=True):
     out = torch.empty(nb, n, d1 + d2, device=DEV)
     idx = torch.empty(nb, n, 3, dtype=torch.int32, device=DEV) if nn else None
     weight = torch.empty(nb, n, 3, device=DEV) if nn else None
-    assert _rc(sim, "ps_cloud_feature_propagation", sim._ctx, _ptr(xyz1), n, _ptr(xyz2), s, _ptr(points1), d1,
+    assert raw_call(sim, "ps_cloud_feature_propagation", sim._ctx, _ptr(xyz1), n, _ptr(xyz2), s, _ptr(points1), d1,
                _ptr(points2), d2, _ptr(out), _ptr(idx), _ptr(weight), sim._stream()) == 0
     return out, idx, weight
 
@@ -216,7 +193,7 @@ def test_fused_equals_the_two_calls_composed(sims, name, with_points1, nn):
 
     only = torch.full_like(idx, -7)
     o2 = torch.empty_like(out)
-    assert _rc(sim, "ps_cloud_feature_propagation", sim._ctx, _ptr(x1), x1.shape[1], _ptr(x2), x2.shape[1], _ptr(p1),
+    assert raw_call(sim, "ps_cloud_feature_propagation", sim._ctx, _ptr(x1), x1.shape[1], _ptr(x2), x2.shape[1], _ptr(p1),
                0 if p1 is None else p1.shape[2], _ptr(p2), p2.shape[2], _ptr(o2), _ptr(only), None,
                sim._stream()) == 0
     assert same_bits(only, idx) and same_bits(o2, composed)
@@ -274,13 +251,13 @@ def test_argument_errors_leave_the_outputs_untouched(sims):
     out = torch.full((2, n, d1 + d2), -7.0, device=DEV)
 
     def nn(context=ctx, a=x1, n_=n, b=x2, s_=s, i=idx, w_=w):
-        return _rc(sim, "ps_cloud_three_nn", context, p(a), n_, p(b), s_, p(i), p(w_), st)
+        return raw_call(sim, "ps_cloud_three_nn", context, p(a), n_, p(b), s_, p(i), p(w_), st)
 
     def interp(context=ctx, f1=p1, d1_=d1, f2=p2, d2_=d2, n_=n, s_=s, i=good_idx, w_=good_w, o=out):
-        return _rc(sim, "ps_cloud_interpolate", context, p(f1), d1_, p(f2), d2_, n_, s_, p(i), p(w_), p(o), st)
+        return raw_call(sim, "ps_cloud_interpolate", context, p(f1), d1_, p(f2), d2_, n_, s_, p(i), p(w_), p(o), st)
 
     def fused(context=ctx, a=x1, n_=n, b=x2, s_=s, f1=p1, d1_=d1, f2=p2, d2_=d2, o=out, i=idx, w_=w):
-        return _rc(sim, "ps_cloud_feature_propagation", context, p(a), n_, p(b), s_, p(f1), d1_, p(f2), d2_, p(o),
+        return raw_call(sim, "ps_cloud_feature_propagation", context, p(a), n_, p(b), s_, p(f1), d1_, p(f2), d2_, p(o),
                    p(i), p(w_), st)
 
     big = (1 << 20) + 1

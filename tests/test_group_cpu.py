@@ -1,7 +1,7 @@
 """CPU tests of the PointNet++ front end (ps_cloud_normalize / _fps /
 _ball_query / _group / _set_abstraction, PandaSim.group_cloud): the numpy
-restatement that tests/test_gpu_group.py holds the kernels to, itself held to
-the golden recorded from the reference (tests/golden/make_group_golden.py), the
+restatement (tests/cloud_reference.py) that tests/test_gpu_group.py holds the
+kernels to, itself held to the golden recorded from the reference (tests/golden/make_group_golden.py), the
 new ABI symbols, and the Python layer's argument checks.
 
 The restatement computes the squared distance directly, d = x - c and
@@ -11,10 +11,12 @@ point within 4e-6 of r^2 (`ambiguous` in the golden) may differ and is skipped
 -- those rows and no others.
 """
 import os
-import re
 
 import numpy as np
 import pytest
+
+from cloud_helpers import assert_abi_topic
+from cloud_reference import ball_query_np, fps_np, group_rows_np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ("A", "B", "C", "D1", "D2", "E")
@@ -22,51 +24,6 @@ QUERY_CASES = ("A", "B", "E")
 MAX_SKIPPED = 0.05
 GROUP_SYMBOLS = ("ps_cloud_normalize", "ps_cloud_fps", "ps_cloud_ball_query", "ps_cloud_group",
                  "ps_cloud_set_abstraction")
-
-
-# --------------------------------------------------------- the restatement
-def d2_direct(xyz, centre):
-    """[N, 3] f32, [3] f32 -> [N] f32: no fused multiply-add (numpy has none)."""
-    d = xyz - centre
-    return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-
-
-def fps_np(xyz, start, s):
-    """farthest_point_sample of one cloud [N, 3] f32 from index `start`."""
-    dist = np.full(xyz.shape[0], 1e10, np.float32)
-    far, idx = int(start), np.empty(s, np.int32)
-    for it in range(s):
-        idx[it] = far
-        dist = np.minimum(dist, d2_direct(xyz, xyz[far]))
-        far = int(np.argmax(dist))  # the lowest index among equal values
-    return idx
-
-
-def ball_query_np(xyz, centre_idx, radius, nsample):
-    """query_ball_point of one cloud with the kernel's own comparison:
-    not d2 > f32(r * r), r * r in f64 -> [S, nsample] i32."""
-    r2 = np.float32(float(radius) * float(radius))
-    out = np.empty((len(centre_idx), nsample), np.int32)
-    for row, c in enumerate(centre_idx):
-        hit = np.nonzero(~(d2_direct(xyz, xyz[c]) > r2))[0][:nsample]
-        out[row, :len(hit)] = hit
-        out[row, len(hit):] = hit[0]
-    return out
-
-
-def group_np(xyz, feats, centre_idx, group_idx):
-    """[S, nsample, D + 3]: feats[group_idx], then xyz[group_idx] - xyz[centre]."""
-    centred = xyz[group_idx] - xyz[centre_idx][:, None, :]
-    return centred if feats is None else np.concatenate([feats[group_idx], centred], -1)
-
-
-def normalize_np(points):
-    """pc_normalize of one cloud in f64 -> xyz, centroid, scale (f64)."""
-    p = points.astype(np.float64)
-    c = p.mean(0)
-    d = p - c
-    m = np.sqrt((d ** 2).sum(1)).max()
-    return (d / m if m > 0 else np.zeros_like(d)), c, m
 
 
 def row_hash(grouped):
@@ -119,8 +76,7 @@ def restated(name):
         for k, (radius, nsample) in enumerate(c["scales"]):
             r[f"group_idx_{k}"] = np.stack([ball_query_np(c["xyz"][b], r["fps_idx"][b], radius, nsample)
                                             for b in range(nb)])
-            r[f"grouped_{k}"] = np.stack([group_np(c["xyz"][b], c["feats"][b], r["fps_idx"][b],
-                                                   r[f"group_idx_{k}"][b]) for b in range(nb)]).astype(np.float32)
+            r[f"grouped_{k}"] = group_rows_np(c["xyz"], c["feats"], r["fps_idx"], r[f"group_idx_{k}"])
         _restated[name] = r
     return _restated[name]
 
@@ -186,18 +142,9 @@ def test_header_and_signatures_carry_the_new_symbols():
 
     from pandasim import _lib as L
 
-    src = open(os.path.join(ROOT, "include", "pandasim.h")).read()
-    names = set(re.findall(r"\b(ps_[a-z_]+)\s*\(", src))
+    src = assert_abi_topic(GROUP_SYMBOLS, "group",
+                           ("PS_CLOUD_MAX_POINTS", "PS_CLOUD_MAX_SCALES", "PS_CLOUD_MAX_FEATURES"))
     lib = L.lib()
-    for s in GROUP_SYMBOLS:
-        assert s in names and s in L.exported_symbols() and hasattr(lib, s), s
-        assert L.SIGNATURES[s][2] == "group"
-        assert getattr(lib, s).restype is C.c_int and len(getattr(lib, s).argtypes) == len(L.SIGNATURES[s][0])
-    assert L.GROUP_SYMBOLS == GROUP_SYMBOLS
-    assert lib.ps_abi_version() == int(re.search(r"#define PS_ABI_VERSION (\d+)", src).group(1)) == 6
-    for macro, value in (("PS_CLOUD_MAX_POINTS", L.CLOUD_MAX_POINTS), ("PS_CLOUD_MAX_SCALES", L.CLOUD_MAX_SCALES),
-                         ("PS_CLOUD_MAX_FEATURES", L.CLOUD_MAX_FEATURES)):
-        assert int(re.search(rf"#define {macro} (\d+)", src).group(1)) == value
     assert L.CLOUD_MAX_POINTS >= 8192 and L.CLOUD_MAX_FEATURES == 16
     assert "ps_cloud_scale" in src and C.sizeof(L.CloudScale) == 32
     assert L.lib().ps_cloud_ball_query.argtypes[5] is C.c_double  # the radius, squared in f64 as the reference's
@@ -207,15 +154,15 @@ def test_header_and_signatures_carry_the_new_symbols():
 
 def test_python_surface_exists():
     import pandasim
-    from pandasim import sim
+    from pandasim import cloudnet
 
     assert hasattr(pandasim.PandaSim, "group_cloud") and hasattr(pandasim.PandaVecEnv, "group_cloud")
-    assert set(sim.GroupedCloud.__slots__) == {"xyz", "centroid", "scale", "fps_idx", "new_xyz", "group_idx",
+    assert set(cloudnet.GroupedCloud.__slots__) == {"xyz", "centroid", "scale", "fps_idx", "new_xyz", "group_idx",
                                                "grouped"}
 
 
 def test_start_is_the_clouds_counter_draw():
-    from pandasim.sim import fps_start
+    from pandasim.cloudnet import fps_start
     from test_cloud_cpu import rank
 
     for seed in (0, 12345, (1 << 64) - 1):
@@ -229,7 +176,7 @@ def test_start_is_the_clouds_counter_draw():
 def test_argument_checks():
     import torch
 
-    from pandasim.sim import group_cloud_args
+    from pandasim.cloudnet import group_cloud_args
 
     pts = torch.zeros(3, 100, 3)
     ok = dict(num_envs=3, points=pts, feats=None, npoint=10, radii=(0.1, 0.2), nsamples=(4, 8), seed=0, start=None)

@@ -1,9 +1,9 @@
 """CPU tests of the shared MLP with max-pool (ps_cloud_mlp, ps_cloud_group_mlp,
 PandaSim.shared_mlp / abstract_features, pandasim.fold_batchnorm): the numpy
-restatement that tests/test_gpu_mlp.py holds the kernels to on every element,
-itself held to the golden recorded from the reference's own modules in float64
-(tests/golden/make_mlp_golden.py), the exact fmaf it is built on, the batch-norm
-fold, the new ABI symbols, and every refusal of the argument functions.
+restatement (tests/cloud_reference.py) that tests/test_gpu_mlp.py holds the
+kernels to on every element, itself held to the golden recorded from the
+reference's own modules in float64 (tests/golden/make_mlp_golden.py), the exact
+fmaf it is built on, the batch-norm fold, the new ABI symbols, and every refusal of the argument functions.
 
 The restatement is include/pandasim.h's chain: y = b; for k ascending
 y = fmaf(x[k], W[o][k], y); ReLU; the maximum over each group.  fma32 is an
@@ -31,81 +31,17 @@ the reference run in f64 subtracts exactly.
 import ctypes
 import ctypes.util
 import os
-import re
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
+from cloud_helpers import assert_abi_topic
+from cloud_reference import fma32, group_rows_np, mlp_np, mlp_with_bound
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -24
 MLP_SYMBOLS = ("ps_cloud_mlp", "ps_cloud_group_mlp")
 CASES = ("msg", "all", "fp")
-
-
-# --------------------------------------------------------- the restatement
-def fma32(a, b, c):
-    """fmaf(a, b, c) on f32 arrays (broadcast), exactly rounded."""
-    p = a.astype(np.float64) * b.astype(np.float64)  # exact
-    c = np.broadcast_to(c.astype(np.float64), p.shape)
-    s = p + c
-    t = s - p
-    err = (p - (s - t)) + (c - t)  # TwoSum: p + c = s + err exactly
-    bits = s.view(np.int64) if s.flags.writeable else s.copy().view(np.int64)
-    fix = (err != 0.0) & ((bits & 1) == 0)
-    # round to odd: the neighbour of s on err's side; |s| grows iff err has s's sign
-    step = np.where((err > 0.0) == (s > 0.0), 1, -1)
-    odd = np.where(fix, bits + step, bits).view(np.float64)
-    return odd.astype(np.float32)
-
-
-def layer_np(x, w, b, relu):
-    """[rows, C_in] f32 -> [rows, C_out] f32: the fmaf chain from the bias."""
-    y = np.broadcast_to(b[None, :], (x.shape[0], w.shape[0])).astype(np.float32)
-    wt = np.ascontiguousarray(w.T)
-    for k in range(w.shape[1]):
-        y = fma32(x[:, k:k + 1], wt[k][None, :], y)
-    return np.where(y > 0, y, np.float32(0)) if relu else y
-
-
-def mlp_np(rows, layers, pool=1):
-    """rows [..., R, C0] f32 -> [..., R / pool, C_n] f32."""
-    lead, r, c0 = rows.shape[:-2], rows.shape[-2], rows.shape[-1]
-    x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, c0)
-    for w, b, relu in layers:
-        x = layer_np(x, w, b, relu)
-    x = x.reshape(*lead, r // pool, pool, x.shape[-1]).max(axis=-2)
-    return x
-
-
-def group_rows_np(xyz, feats, centre_idx, group_idx, dtype=np.float32):
-    """ps_cloud_group's rows: [B, S, K, D + 3] = feats[group_idx], then
-    xyz[group_idx] - xyz[centre_idx] in f32 (in xyz's own precision with
-    another dtype)."""
-    out = []
-    for b in range(xyz.shape[0]):
-        rel = xyz[b][group_idx[b]] - xyz[b][centre_idx[b]][:, None, :]
-        out.append(rel if feats is None else np.concatenate([feats[b][group_idx[b]], rel], -1))
-    return np.stack(out).astype(dtype)
-
-
-def mlp_with_bound(rows, layers, pool=1, centred=0):
-    """mlp_np and, beside it, the bound on its distance from the exact
-    arithmetic of the unfolded f64 layers (the module docstring).  The last
-    `centred` input columns are f32 differences (ps_cloud_group's centring),
-    each one rounding away from the reference's f64 difference: u |x| there."""
-    lead, r, c0 = rows.shape[:-2], rows.shape[-2], rows.shape[-1]
-    x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, c0)
-    e = np.zeros(x.shape)
-    if centred:
-        e[:, c0 - centred:] = U * np.abs(x[:, c0 - centred:].astype(np.float64))
-    for w, b, relu in layers:
-        aw, ab, ax = np.abs(w.astype(np.float64)), np.abs(b.astype(np.float64)), np.abs(x.astype(np.float64))
-        mag = ax @ aw.T + ab[None, :]
-        e = 1.01 * ((w.shape[1] + 1) * U * mag + e @ aw.T + U * (mag + e @ aw.T))
-        x = layer_np(x, w, b, relu)
-    shape = (*lead, r // pool, pool, x.shape[-1])
-    return x.reshape(shape).max(axis=-2), e.reshape(shape).max(axis=-2)
 
 
 # ------------------------------------------------------------- the golden
@@ -280,21 +216,8 @@ def test_header_and_signatures_carry_the_new_symbols():
 
     from pandasim import _lib as L
 
-    src = open(os.path.join(ROOT, "include", "pandasim.h")).read()
-    names = set(re.findall(r"\b(ps_[a-z_]+)\s*\(", src))
-    lib = L.lib()
-    for s in MLP_SYMBOLS:
-        assert s in names and s in L.exported_symbols() and hasattr(lib, s), s
-        assert L.SIGNATURES[s][2] == "mlp"
-        assert getattr(lib, s).restype is C.c_int and len(getattr(lib, s).argtypes) == len(L.SIGNATURES[s][0])
-        decl = re.search(rf"\bint {s}\s*\(([^;]*)\);", src).group(1)
-        assert len(decl.split(",")) == len(L.SIGNATURES[s][0]), s
-    assert L.MLP_SYMBOLS == MLP_SYMBOLS
-    assert lib.ps_abi_version() == int(re.search(r"#define PS_ABI_VERSION (\d+)", src).group(1)) == 6
-    for macro, value in (("PS_CLOUD_MLP_MAX_LAYERS", L.CLOUD_MLP_MAX_LAYERS),
-                         ("PS_CLOUD_MLP_MAX_HIDDEN", L.CLOUD_MLP_MAX_HIDDEN),
-                         ("PS_CLOUD_MLP_MAX_LAST", L.CLOUD_MLP_MAX_LAST)):
-        assert int(re.search(rf"#define {macro} (\d+)", src).group(1)) == value
+    assert_abi_topic(MLP_SYMBOLS, "mlp",
+                     ("PS_CLOUD_MLP_MAX_LAYERS", "PS_CLOUD_MLP_MAX_HIDDEN", "PS_CLOUD_MLP_MAX_LAST"))
     assert (L.CLOUD_MLP_MAX_LAYERS, L.CLOUD_MLP_MAX_HIDDEN, L.CLOUD_MLP_MAX_LAST) == (4, 512, 1024)
     # ps_cloud_mlp_layer: two pointers and two i32
     assert C.sizeof(L.CloudMlpLayer) == 24 and L.CloudMlpLayer.c_out.offset == 16 and L.CloudMlpLayer.relu.offset == 20
@@ -335,7 +258,7 @@ def test_fold_batchnorm_refusals():
 
 
 def test_cloud_mlp_layer_refusals():
-    from pandasim.sim import cloud_mlp_layers
+    from pandasim.cloudnet import cloud_mlp_layers
 
     f = np.float32
     lay = lambda o, i: (np.zeros((o, i), f), np.zeros(o, f), True)  # noqa: E731
@@ -365,7 +288,7 @@ def test_cloud_mlp_layer_refusals():
 def test_shared_mlp_argument_checks():
     import torch
 
-    from pandasim.sim import shared_mlp_args
+    from pandasim.cloudnet import shared_mlp_args
 
     mlp = fake_mlp(9, [32, 64])
     ok = dict(num_envs=3, rows=torch.zeros(3, 12, 9), layers=mlp, pool=4, out=None, out_offset=0)
@@ -385,7 +308,7 @@ def test_shared_mlp_argument_checks():
 def test_abstract_features_argument_checks():
     import torch
 
-    from pandasim.sim import abstract_features_args
+    from pandasim.cloudnet import abstract_features_args
 
     i32 = torch.int32
     ok = dict(num_envs=2, xyz=torch.zeros(2, 50, 3), feats=torch.zeros(2, 50, 6), centre_idx=torch.zeros(2, 8, dtype=i32),

@@ -1,9 +1,9 @@
 """CPU tests of the PointNet++ feature propagation (ps_cloud_three_nn /
 _interpolate / _feature_propagation, PandaSim.propagate_features): the numpy
-restatement that tests/test_gpu_propagate.py holds the kernels to bit for bit,
-itself held to the golden recorded from the reference's
-PointNetFeaturePropagation in float64 (tests/golden/make_propagate_golden.py),
-the new ABI symbols, and the Python layer's argument checks.
+restatement (tests/cloud_reference.py) that tests/test_gpu_propagate.py holds
+the kernels to bit for bit, itself held to the golden recorded from the
+reference's PointNetFeaturePropagation in float64
+(tests/golden/make_propagate_golden.py), the new ABI symbols, and the Python layer's argument checks.
 
 The bound of the restatement against the f64 golden, per cloud:
     |restatement - golden| <= K * eps_f32 * max|points2|,  K = 12.
@@ -26,10 +26,12 @@ added to.  Rows marked ambiguous in the golden (3rd and 4th nearest within
 4e-6 in f32) are skipped, those and no others.
 """
 import os
-import re
 
 import numpy as np
 import pytest
+
+from cloud_helpers import assert_abi_topic
+from cloud_reference import propagate_np, three_nn_np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ("A", "B", "C", "D", "E")
@@ -39,54 +41,6 @@ MAX_SKIPPED = 0.05
 K_BOUND = 12
 EPS = float(np.finfo(np.float32).eps)
 PROPAGATE_SYMBOLS = ("ps_cloud_three_nn", "ps_cloud_interpolate", "ps_cloud_feature_propagation")
-
-
-# --------------------------------------------------------- the restatement
-def d2_matrix(xyz1, xyz2):
-    """[N, 3], [S, 3] f32 -> [N, S] f32: d = a - b, (d.x*d.x + d.y*d.y) + d.z*d.z,
-    every product and sum rounded (numpy has no fused multiply-add)."""
-    d = xyz1[:, None, :] - xyz2[None, :, :]
-    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-
-
-def three_nn_np(xyz1, xyz2):
-    """One cloud -> idx [N, 3] i32, weight [N, 3] f32.  A stable sort: ascending
-    distance, the lowest index first among equal values."""
-    n, s = xyz1.shape[0], xyz2.shape[0]
-    if s == 1:
-        return np.zeros((n, 3), np.int32), np.tile(np.array([1, 0, 0], np.float32), (n, 1))
-    idx = np.empty((n, 3), np.int32)
-    d3 = np.empty((n, 3), np.float32)
-    for lo in range(0, n, 4096):  # in slabs, to bound the matrix
-        d2 = d2_matrix(xyz1[lo:lo + 4096], xyz2)
-        order = np.argsort(d2, axis=1, kind="stable")[:, :3]
-        idx[lo:lo + 4096] = order
-        d3[lo:lo + 4096] = np.take_along_axis(d2, order, axis=1)
-    w = np.float32(1.0) / (d3 + np.float32(1e-8))
-    norm = (w[:, 0] + w[:, 1]) + w[:, 2]
-    return idx, (w / norm[:, None]).astype(np.float32)
-
-
-def interpolate_np(points1, points2, idx, weight):
-    """One cloud -> [N, D1 + D2] f32: points1, then (p0*w0 + p1*w1) + p2*w2."""
-    if points2.shape[0] == 1:
-        interp = np.repeat(points2, idx.shape[0], axis=0)
-    else:
-        t = points2[idx] * weight[:, :, None]  # [N, 3, D2], each product rounded
-        interp = (t[:, 0] + t[:, 1]) + t[:, 2]
-    interp = interp.astype(np.float32)
-    return interp if points1 is None else np.concatenate([points1, interp], -1)
-
-
-def propagate_np(xyz1, xyz2, points2, points1=None):
-    """Batched: -> out [B, N, D1 + D2], idx [B, N, 3], weight [B, N, 3]."""
-    outs, idxs, ws = [], [], []
-    for b in range(xyz1.shape[0]):
-        idx, w = three_nn_np(xyz1[b], xyz2[b])
-        outs.append(interpolate_np(None if points1 is None else points1[b], points2[b], idx, w))
-        idxs.append(idx)
-        ws.append(w)
-    return np.stack(outs), np.stack(idxs), np.stack(ws)
 
 
 # -------------------------------------------------------------- the golden
@@ -169,25 +123,11 @@ def test_ties_go_to_the_lowest_index_and_zero_distance_is_finite():
 
 # ----------------------------------------------------------------- the ABI
 def test_header_and_signatures_carry_the_new_symbols():
-    import ctypes as C
-
     from pandasim import _lib as L
 
-    src = open(os.path.join(ROOT, "include", "pandasim.h")).read()
-    names = set(re.findall(r"\b(ps_[a-z_]+)\s*\(", src))
+    assert_abi_topic(PROPAGATE_SYMBOLS, "propagate", ("PS_CLOUD_MAX_POINTS", "PS_CLOUD_MAX_FEATURES",
+                                                      "PS_CLOUD_MAX_PROP_FEATURES", "PS_CLOUD_MAX_DENSE_POINTS"))
     lib = L.lib()
-    for s in PROPAGATE_SYMBOLS:
-        assert s in names and s in L.exported_symbols() and hasattr(lib, s), s
-        assert L.SIGNATURES[s][2] == "propagate"
-        assert getattr(lib, s).restype is C.c_int and len(getattr(lib, s).argtypes) == len(L.SIGNATURES[s][0])
-        decl = re.search(rf"\bint {s}\s*\(([^;]*)\);", src).group(1)
-        assert len(decl.split(",")) == len(L.SIGNATURES[s][0]), s
-    assert L.PROPAGATE_SYMBOLS == PROPAGATE_SYMBOLS
-    assert lib.ps_abi_version() == int(re.search(r"#define PS_ABI_VERSION (\d+)", src).group(1)) == 6
-    for macro, value in (("PS_CLOUD_MAX_POINTS", L.CLOUD_MAX_POINTS), ("PS_CLOUD_MAX_FEATURES", L.CLOUD_MAX_FEATURES),
-                         ("PS_CLOUD_MAX_PROP_FEATURES", L.CLOUD_MAX_PROP_FEATURES),
-                         ("PS_CLOUD_MAX_DENSE_POINTS", L.CLOUD_MAX_DENSE_POINTS)):
-        assert int(re.search(rf"#define {macro} (\d+)", src).group(1)) == value
     assert L.CLOUD_MAX_PROP_FEATURES == 2048 and L.CLOUD_MAX_DENSE_POINTS == 1 << 20 and L.CLOUD_MAX_FEATURES == 16
     # a NULL context is refused before anything else is looked at
     assert L.ERRORS[lib.ps_cloud_three_nn(None, None, 5, None, 3, None, None, None)] == "PS_ERR_ARG"
@@ -204,7 +144,7 @@ def test_python_surface_exists():
 def test_argument_checks():
     import torch
 
-    from pandasim.sim import propagate_features_args
+    from pandasim.cloudnet import propagate_features_args
 
     ok = dict(num_envs=3, xyz1=torch.zeros(3, 100, 3), xyz2=torch.zeros(3, 10, 3), points2=torch.zeros(3, 10, 8),
               points1=None)

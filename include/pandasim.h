@@ -639,6 +639,68 @@ int ps_cloud_group_mlp(ps_ctx *ctx, const float *xyz, const float *feats, int N,
                        int S, const int32_t *group_idx, int K, const ps_cloud_mlp_layer *layers, int n_layers,
                        float *out, int64_t out_stride, int out_offset, void *stream);
 
+/* --- Point-cloud policy: waypoint decoding --- */
+
+/* What envs/inference/inference_cls_off_rot.py: Inference.predict does after
+ * the classifier (lines 68-107), for the context's B clouds in one launch, one
+ * workgroup per cloud, every head row read once.
+ *
+ * head [B, N, ld] f32 is the network's last layer, one row per point: columns
+ * 0 .. nc-1 the class logits, then the start offset (3), the end offset (3),
+ * the start quaternion xyzw (4) and the end quaternion xyzw (4); columns from
+ * nc + 14 on are not read.  xyz [B, N, 3] f32 are the normalised points,
+ * centroid [B, 3] and scale [B] f32 the cloud's normalisation (both NULL: no
+ * un-normalisation, the same values as centroid 0 and scale 1).  Bit c of
+ * start_mask / end_mask set means class c belongs to the start / end set; the
+ * reference's sets (classes 1 and 3, classes 2 and 3) are 0b1010 and 0b1100.
+ * Set 0 below is the start set, set 1 the end set.
+ *
+ *   Label.      best = logit[0], label = 0; for c = 1 .. nc-1 ascending:
+ *               if logit[c] > best, best = logit[c] and label = c.  The lowest
+ *               index wins a tie; a NaN logit never wins.  (The one deviation:
+ *               the reference takes the max of softmax(log_softmax(logits)),
+ *               whose roundings can merge two close logits into a tie.)
+ *   Waypoint.   (the mean over the set's points of (xyz - offset)) * scale +
+ *               centroid.  Each difference is taken in f64 from the f32
+ *               operands, the sums are f64 in a fixed order (thread t of the
+ *               T = 1024 of a workgroup takes points t, t + T, ... ascending;
+ *               the T partial sums are added by halving in LDS: partial t takes
+ *               partial t + h for h = T/2, T/4, ... 1), the mean, the product
+ *               and the sum with the centroid are f64, and the result is
+ *               rounded to f32 once.  No atomics: the bits of cloud b depend
+ *               on nothing but cloud b's inputs.
+ *   Quaternion. The head's quaternion of the set at the lowest point index in
+ *               the set (the reference's np.union1d(...)[0]), each component
+ *               divided in f32 by the norm, the norm being the f64 square root
+ *               of the f64 sum of squares rounded to f32.  A zero quaternion
+ *               gives NaN, as in the reference.
+ *   Euler.      scipy's 'xyz' (extrinsic) in degrees of that normalised
+ *               quaternion, evaluated in f64 and rounded to f32:
+ *               roll  = atan2(2 (w x + y z), 1 - 2 (x x + y y)),
+ *               pitch = asin(clamp(2 (w y - z x), -1, 1)),
+ *               yaw   = atan2(2 (w z + x y), 1 - 2 (y y + z z)).
+ *   Empty set.  The reference raises.  Here counts = 0, first_idx = -1 and that
+ *               set's waypoint, quaternion and Euler angles are NaN; nothing is
+ *               left unwritten.
+ *
+ * Outputs: waypoints [B, 2, 3] f32, quats [B, 2, 4] f32 (normalised xyzw),
+ * euler_deg [B, 2, 3] f32, counts [B, 2] i32 (the sets' sizes), labels [B, N]
+ * i32 (may be NULL), first_idx [B, 2] i32 (the lowest point index of each set
+ * or -1; may be NULL).
+ *
+ * Limits (PS_ERR_ARG, nothing launched, outputs untouched): a NULL required
+ * pointer, N outside 1..PS_CLOUD_MAX_DENSE_POINTS, nc outside
+ * 2..PS_CLOUD_DECODE_MAX_CLASSES, ld outside nc + 14 .. PS_CLOUD_DECODE_MAX_LD,
+ * a mask that is zero or has a bit at or above nc, centroid and scale not both
+ * present or both NULL.  Inputs are addressed with 64-bit offsets. */
+#define PS_CLOUD_DECODE_MAX_CLASSES 16
+#define PS_CLOUD_DECODE_MAX_LD 4096
+
+int ps_cloud_decode_waypoints(ps_ctx *ctx, const float *head, int N, int ld, int nc, const float *xyz,
+                              const float *centroid, const float *scale, uint32_t start_mask, uint32_t end_mask,
+                              float *waypoints, float *quats, float *euler_deg, int32_t *counts, int32_t *labels,
+                              int32_t *first_idx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,10 @@
-"""The batched PointNet++ layer over a point-cloud observation (DESIGN.md §11.3-11.5):
-sampling and grouping, feature propagation, the shared MLP with max-pool.
+"""The batched PointNet++ layer over a point-cloud observation (DESIGN.md §11.3-11.6):
+sampling and grouping, feature propagation, the shared MLP with max-pool, and
+the policy they compose: the network's forward and the waypoint decoding.
 
 ``CloudNet`` is a mixin of ``PandaSim``; the checkers, ``GroupedCloud``,
-``CloudMlp`` and ``fold_batchnorm`` beside it need no simulator at all.
+``CloudMlp``, ``fold_batchnorm``, ``CloudSegNet`` and ``DecodedWaypoints``
+beside it need no simulator at all.
 """
 from __future__ import annotations
 
@@ -16,7 +18,8 @@ from ._lib import _ptr
 
 
 class CloudNet:
-    """group_cloud, propagate_features, shared_mlp and abstract_features for B
+    """group_cloud, propagate_features, shared_mlp, abstract_features and, on top
+    of them, segment_cloud, decode_waypoints and predict_waypoints for B
     clouds.  They read no simulator state.  The host class provides exactly
     ``self.num_envs`` (B), ``self.device`` (a torch.device), ``self._ctx`` (a
     library context of B envs on that device), ``self._call(name, *args)``
@@ -160,6 +163,79 @@ class CloudNet:
                 self._call("ps_cloud_mlp", self._ctx, _ptr(grouped), S * K, D + 3, mlp.array, len(mlp), K, _ptr(out),
                            width, off, self._stream())
         return out
+
+    def decode_waypoints(self, head, xyz, num_classes: int, centroid=None, scale=None, start_classes=(1, 3),
+                         end_classes=(2, 3), return_labels: bool = False) -> "DecodedWaypoints":
+        """What Inference.predict does after the classifier
+        (inference_cls_off_rot.py:68-107) -- fused (ps_cloud_decode_waypoints),
+        for every env, on the device: per point the arg-max class (the lowest
+        index among equal logits), the start and the end point set (the points
+        labelled with one of start_classes / end_classes), per set the mean of
+        point - offset times scale plus centroid (f64 sums in a fixed order),
+        and the quaternion predicted at the set's first point, normalised and
+        as scipy's 'xyz' Euler degrees.  An empty set gives count 0, first_idx
+        -1 and NaN, where the reference raises.
+
+        head [B, N, ld] f32 with ld >= num_classes + 14: the logits, then start
+        offset (3), end offset (3), start quaternion xyzw (4), end quaternion
+        (4); xyz [B, N, 3] f32 the normalised points; centroid [B, 3] and scale
+        [B] f32 (a GroupedCloud's), or both None for no un-normalisation.
+        Returns a DecodedWaypoints."""
+        B, dev = self.num_envs, self.device
+        head, xyz = torch.as_tensor(head, device=dev), torch.as_tensor(xyz, device=dev)
+        if centroid is not None:
+            centroid = torch.as_tensor(centroid, device=dev)
+        if scale is not None:
+            scale = torch.as_tensor(scale, device=dev)
+        N, ld, nc, masks = decode_waypoints_args(B, head, xyz, num_classes, centroid, scale, start_classes, end_classes)
+        head, xyz = head.contiguous(), xyz.contiguous()
+        centroid = None if centroid is None else centroid.contiguous()
+        scale = None if scale is None else scale.contiguous()
+        out = DecodedWaypoints()
+        out.waypoints = torch.empty(B, 2, 3, dtype=torch.float32, device=dev)
+        out.quats = torch.empty(B, 2, 4, dtype=torch.float32, device=dev)
+        out.euler_deg = torch.empty(B, 2, 3, dtype=torch.float32, device=dev)
+        out.counts = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        out.first_idx = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        out.labels = torch.empty(B, N, dtype=torch.int32, device=dev) if return_labels else None
+        self._call("ps_cloud_decode_waypoints", self._ctx, _ptr(head), N, ld, nc, _ptr(xyz), _ptr(centroid), _ptr(scale),
+                   masks[0], masks[1], _ptr(out.waypoints), _ptr(out.quats), _ptr(out.euler_deg), _ptr(out.counts),
+                   _ptr(out.labels), _ptr(out.first_idx), self._stream())
+        return out
+
+    def segment_cloud(self, net: "CloudSegNet", points, colors, seed: int = 0, normalize: bool = True):
+        """model_cls_off_rot.py: get_model.forward at inference, for every env
+        (DESIGN.md §11.6 restates the wiring): sa1, sa2, sa3, fp3, fp2, fp1,
+        conv1 / bn1, conv2, composed of group_cloud, abstract_features,
+        propagate_features and shared_mlp.  Farthest point sampling starts from
+        fps_start(seed, b, N) at sa1 and fps_start(seed + 1, b, 512) at sa2.
+
+        points [B, N, 3] f32 with 512 <= N <= CLOUD_MAX_POINTS, colors
+        [B, N, C - 3] f32 (C net.num_input_channels).  Returns head
+        [B, N, num_classes + 14] f32 (the reference's x before its
+        log_softmax, one row per point) and level 1's GroupedCloud, whose xyz,
+        centroid and scale decode_waypoints takes."""
+        B, dev = self.num_envs, self.device
+        points, colors = torch.as_tensor(points, device=dev), torch.as_tensor(colors, device=dev)
+        segment_cloud_args(B, net, points, colors)
+        g1 = self.group_cloud(points, None, net.SA1_NPOINT, net.SA1_RADII, net.SA1_NSAMPLES, seed, normalize)
+        l0 = torch.cat([g1.xyz, colors], dim=2)
+        l1 = self.abstract_features(g1, l0, mlps=net.sa1)
+        g2 = self.group_cloud(g1.new_xyz, None, net.SA2_NPOINT, net.SA2_RADII, net.SA2_NSAMPLES, seed + 1,
+                              normalize=False)
+        l2 = self.abstract_features(g2, l1, mlps=net.sa2)
+        l3 = self.shared_mlp(torch.cat([g2.new_xyz, l2], dim=2), net.sa3, pool=net.SA2_NPOINT)
+        origin = torch.zeros(B, 1, 3, dtype=torch.float32, device=dev)
+        l2 = self.shared_mlp(self.propagate_features(g2.new_xyz, origin, l3, l2), net.fp3)
+        l1 = self.shared_mlp(self.propagate_features(g1.new_xyz, g2.new_xyz, l2, l1), net.fp2)
+        l0 = self.shared_mlp(self.propagate_features(g1.xyz, g1.new_xyz, l1, torch.cat([g1.xyz, l0], dim=2)), net.fp1)
+        return self.shared_mlp(l0, net.head), g1
+
+    def predict_waypoints(self, net: "CloudSegNet", points, colors, seed: int = 0) -> "DecodedWaypoints":
+        """The batched Inference.predict: segment_cloud, then decode_waypoints
+        with that cloud's centroid and scale."""
+        head, g1 = self.segment_cloud(net, points, colors, seed)
+        return self.decode_waypoints(head, g1.xyz, net.num_classes, g1.centroid, g1.scale)
 
 
 class GroupedCloud:
@@ -404,3 +480,177 @@ def abstract_features_args(num_envs: int, xyz, feats, centre_idx, group_idx, mlp
         offsets.append(width)
         width += mlp.widths[-1]
     return N, S, D, offsets, width
+
+
+# ------------------------------------------------------------ the policy
+class DecodedWaypoints:
+    """PandaSim.decode_waypoints' result; index 0 of the second dimension is the
+    start set, 1 the end set: waypoints [B, 2, 3] f32, quats [B, 2, 4] f32
+    (normalised xyzw), euler_deg [B, 2, 3] f32 (scipy's 'xyz', what
+    step(..., euler_xyz=...) takes), counts [B, 2] i32 (the sets' sizes),
+    first_idx [B, 2] i32 (the lowest point index of each set, -1 for an empty
+    one, whose waypoint, quaternion and angles are NaN) and labels [B, N] i32
+    (None unless asked for)."""
+
+    __slots__ = ("waypoints", "quats", "euler_deg", "counts", "first_idx", "labels")
+
+
+def _class_mask(name: str, classes, nc: int) -> int:
+    try:
+        classes = list(classes)
+    except TypeError:
+        raise ValueError(f"decode_waypoints: {name} must be a sequence of class indices") from None
+    mask = 0
+    for c in classes:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < nc:
+            raise ValueError(f"decode_waypoints: {name} holds {c!r} (whole numbers from 0 to num_classes - 1 = {nc - 1})")
+        mask |= 1 << int(c)
+    if mask == 0:
+        raise ValueError(f"decode_waypoints: {name} is empty")
+    return mask
+
+
+def decode_waypoints_args(num_envs: int, head, xyz, num_classes, centroid, scale, start_classes, end_classes):
+    """decode_waypoints' argument checks (ValueError), on tensors of any
+    device: -> N, ld, num_classes and the two class masks."""
+    B = int(num_envs)
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or \
+            not 2 <= num_classes <= L.CLOUD_DECODE_MAX_CLASSES:
+        raise ValueError(f"decode_waypoints: num_classes = {num_classes!r} (a whole number from 2 to "
+                         f"{L.CLOUD_DECODE_MAX_CLASSES})")
+    nc = int(num_classes)
+    _want("decode_waypoints", "head", head, (B, "N", "ld"))
+    N, ld = int(head.shape[1]), int(head.shape[2])
+    if not 1 <= N <= L.CLOUD_MAX_DENSE_POINTS:
+        raise ValueError(f"decode_waypoints: N = {N} points (1 to {L.CLOUD_MAX_DENSE_POINTS})")
+    if not nc + 14 <= ld <= L.CLOUD_DECODE_MAX_LD:
+        raise ValueError(f"decode_waypoints: head rows of {ld} columns (num_classes + 14 = {nc + 14} to "
+                         f"{L.CLOUD_DECODE_MAX_LD}: logits, two offsets, two quaternions)")
+    _want("decode_waypoints", "xyz", xyz, (B, N, 3))
+    if (centroid is None) != (scale is None):
+        raise ValueError("decode_waypoints: centroid and scale go together (both, or neither for no un-normalisation)")
+    if centroid is not None:
+        _want("decode_waypoints", "centroid", centroid, (B, 3))
+        _want("decode_waypoints", "scale", scale, (B,))
+    return N, ld, nc, (_class_mask("start_classes", start_classes, nc), _class_mask("end_classes", end_classes, nc))
+
+
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+
+
+def _state_array(state, key: str):
+    if key not in state:
+        raise ValueError(f"CloudSegNet: the state has no {key}")
+    a = state[key]
+    return np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+
+
+def _state_layer(state, conv: str, bn, c_in: int, relu: bool, eps: float):
+    """One layer of a CloudMlp from the state: `conv` (+ `bn` folded in)."""
+    w = _state_array(state, conv + ".weight")
+    if not 2 <= w.ndim <= 4 or any(d != 1 for d in w.shape[2:]) or w.shape[0] < 1 or w.shape[1] != c_in:
+        raise ValueError(f"CloudSegNet: {conv}.weight must be [c_out, {c_in}, 1(, 1)] (the layer before it gives "
+                         f"{c_in} channels), got {w.shape}")
+    c_out, vec = int(w.shape[0]), []
+    for key in [conv + ".bias"] + [f"{bn}.{n}" for n in (_BN_KEYS if bn else ())]:
+        a = _state_array(state, key)
+        if a.shape != (c_out,):
+            raise ValueError(f"CloudSegNet: {key} must be [{c_out}], got {a.shape}")
+        vec.append(a)
+    if bn is None:
+        return w.reshape(c_out, c_in).astype(np.float32), vec[0].astype(np.float32), relu
+    try:
+        return (*fold_batchnorm(w, *vec, eps), relu)
+    except ValueError as e:
+        raise ValueError(f"CloudSegNet: {bn}: {e}") from None
+
+
+def _state_chain(state, convs: str, bns: str, c_in: int, eps: float):
+    """The layers `convs`.0, .1, ... with their batch norms -> a CloudMlp's list."""
+    layers, j = [], 0
+    while j == 0 or f"{convs}.{j}.weight" in state:
+        layers.append(_state_layer(state, f"{convs}.{j}", f"{bns}.{j}", c_in, True, eps))
+        c_in, j = int(layers[-1][0].shape[0]), j + 1
+    if any(k.startswith((f"{convs}.{j}.", f"{bns}.{j}.")) for k in state):  # a later layer's other keys
+        raise ValueError(f"CloudSegNet: the state has no {convs}.{j}.weight")
+    return layers
+
+
+def segnet_layers(state, eps: float = 1e-5):
+    """CloudSegNet's host half (ValueError naming the key that is missing or
+    mis-shaped): the state_dict of a model_cls_off_rot.get_model, key ->
+    array or tensor, as the folded layer lists of its seven shared MLPs:
+    -> ({"sa1": [3 lists], "sa2": [2 lists], "sa3", "fp3", "fp2", "fp1",
+    "head": lists of (W f32, b f32, relu)}, num_classes, num_input_channels).
+    `eps` is the batch norms' (not part of a state_dict; torch's default)."""
+    w0 = _state_array(state, "sa1.conv_blocks.0.0.weight")
+    C = (int(w0.shape[1]) if w0.ndim >= 2 else 0) - 3
+    if C < 3:
+        raise ValueError(f"CloudSegNet: sa1.conv_blocks.0.0.weight must take num_input_channels + 3 >= 6 channels, "
+                         f"got {w0.shape}")
+    out = {}
+    c_in = C
+    for name, scales in (("sa1", len(CloudSegNet.SA1_RADII)), ("sa2", len(CloudSegNet.SA2_RADII))):
+        if f"{name}.conv_blocks.{scales}.0.weight" in state:
+            raise ValueError(f"CloudSegNet: {name}.conv_blocks.{scales}.0.weight: {name} has {scales} scales")
+        out[name] = [_state_chain(state, f"{name}.conv_blocks.{i}", f"{name}.bn_blocks.{i}", c_in + 3, eps)
+                     for i in range(scales)]
+        c_in = sum(int(mlp[-1][0].shape[0]) for mlp in out[name])
+    w1, w2 = (sum(int(mlp[-1][0].shape[0]) for mlp in out[n]) for n in ("sa1", "sa2"))
+    out["sa3"] = _state_chain(state, "sa3.mlp_convs", "sa3.mlp_bns", w2 + 3, eps)
+    out["fp3"] = _state_chain(state, "fp3.mlp_convs", "fp3.mlp_bns", w2 + int(out["sa3"][-1][0].shape[0]), eps)
+    out["fp2"] = _state_chain(state, "fp2.mlp_convs", "fp2.mlp_bns", w1 + int(out["fp3"][-1][0].shape[0]), eps)
+    out["fp1"] = _state_chain(state, "fp1.mlp_convs", "fp1.mlp_bns", 3 + C + int(out["fp2"][-1][0].shape[0]), eps)
+    conv1 = _state_layer(state, "conv1", "bn1", int(out["fp1"][-1][0].shape[0]), True, eps)
+    conv2 = _state_layer(state, "conv2", None, int(conv1[0].shape[0]), False, eps)
+    nc = int(conv2[0].shape[0]) - CloudSegNet.NUM_OUTPUT_CHANNELS
+    if not 2 <= nc <= L.CLOUD_DECODE_MAX_CLASSES:
+        raise ValueError(f"CloudSegNet: conv2.weight must give num_classes + {CloudSegNet.NUM_OUTPUT_CHANNELS} "
+                         f"channels with 2 to {L.CLOUD_DECODE_MAX_CLASSES} classes, got {conv2[0].shape[0]}")
+    out["head"] = [conv1, conv2]
+    return out, nc, C
+
+
+class CloudSegNet:
+    """The weights of one model_cls_off_rot.get_model at inference, for
+    PandaSim.segment_cloud / predict_waypoints: built from a mapping with the
+    reference's state_dict key names (sa1.conv_blocks.0.0.weight,
+    sa1.bn_blocks.0.0.running_var, sa3.mlp_convs.1.bias, fp2.mlp_bns.0.weight,
+    conv1.weight, bn1.running_mean, conv2.bias, ...; num_batches_tracked is not
+    read) to arrays or tensors.  Every conv + bn pair is folded
+    (fold_batchnorm) into a CloudMlp on `device`: sa1 and sa2 are lists of one
+    per scale, sa3, fp3, fp2, fp1 one each, head is conv1 + bn1 with ReLU then
+    conv2 without (dropout is the identity at inference).  num_classes,
+    num_input_channels and every width come from the shapes; a missing or
+    mis-shaped key raises ValueError naming it.  The sampling constants are the
+    reference's (model_cls_off_rot.py:12-14)."""
+
+    SA1_NPOINT, SA1_RADII, SA1_NSAMPLES = 512, (0.1, 0.2, 0.4), (32, 64, 128)
+    SA2_NPOINT, SA2_RADII, SA2_NSAMPLES = 128, (0.4, 0.8), (64, 128)
+    NUM_OUTPUT_CHANNELS = 14  # two offsets and two quaternions behind the logits
+
+    def __init__(self, state, device="cuda", eps: float = 1e-5):
+        layers, self.num_classes, self.num_input_channels = segnet_layers(state, eps)
+        self.device = torch.device(device)
+        self.sa1 = [CloudMlp(mlp, self.device) for mlp in layers["sa1"]]
+        self.sa2 = [CloudMlp(mlp, self.device) for mlp in layers["sa2"]]
+        self.sa3, self.fp3, self.fp2, self.fp1, self.head = (CloudMlp(layers[n], self.device)
+                                                             for n in ("sa3", "fp3", "fp2", "fp1", "head"))
+        self.widths = {n: [m.widths for m in v] if isinstance(v, list) else v.widths
+                       for n, v in (("sa1", self.sa1), ("sa2", self.sa2), ("sa3", self.sa3), ("fp3", self.fp3),
+                                    ("fp2", self.fp2), ("fp1", self.fp1), ("head", self.head))}
+
+
+def segment_cloud_args(num_envs: int, net, points, colors) -> int:
+    """segment_cloud's argument checks (ValueError), on tensors of any device:
+    -> N."""
+    B = int(num_envs)
+    if not all(hasattr(net, a) for a in ("sa1", "sa2", "sa3", "fp3", "fp2", "fp1", "head", "num_input_channels")):
+        raise ValueError(f"segment_cloud: net must be a CloudSegNet, got {type(net).__name__}")
+    _want("segment_cloud", "points", points, (B, "N", 3))
+    N = int(points.shape[1])
+    if not net.SA1_NPOINT <= N <= L.CLOUD_MAX_POINTS:
+        raise ValueError(f"segment_cloud: N = {N} points ({net.SA1_NPOINT}, the centres of sa1, to "
+                         f"{L.CLOUD_MAX_POINTS})")
+    _want("segment_cloud", "colors", colors, (B, N, net.num_input_channels - 3))
+    return N

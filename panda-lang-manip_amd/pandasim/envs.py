@@ -240,6 +240,23 @@ class PandaVecEnv:
         cloud (PandaSim.abstract_features)."""
         return self.sim.abstract_features(xyz, feats, centre_idx, group_idx, mlps, fused)
 
+    def decode_waypoints(self, head, xyz, num_classes, centroid=None, scale=None, start_classes=(1, 3),
+                         end_classes=(2, 3), return_labels: bool = False):
+        """The policy's waypoints and orientations of every env's cloud from
+        the network's last layer (PandaSim.decode_waypoints)."""
+        return self.sim.decode_waypoints(head, xyz, num_classes, centroid, scale, start_classes, end_classes,
+                                         return_labels)
+
+    def segment_cloud(self, net, points, colors, seed: int = 0, normalize: bool = True):
+        """The point-cloud policy's network on every env's cloud
+        (PandaSim.segment_cloud)."""
+        return self.sim.segment_cloud(net, points, colors, seed, normalize)
+
+    def predict_waypoints(self, net, points, colors, seed: int = 0):
+        """Cloud to waypoints and orientations for every env
+        (PandaSim.predict_waypoints)."""
+        return self.sim.predict_waypoints(net, points, colors, seed)
+
     def close(self) -> None:
         self.sim.close()
 

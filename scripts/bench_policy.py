@@ -1,0 +1,169 @@
+#!/usr/bin/env python
+"""The point-cloud policy (PandaSim.segment_cloud and decode_waypoints) at the
+reference's shape, N = 5 000 points per cloud, with seeded weights of
+model_cls_off_rot.get_model(14, 6, 4):
+
+stages   device-event time of each stage of segment_cloud's wiring (DESIGN.md
+         §11.6), the stages run one after the other as segment_cloud runs them:
+         sa1 group / sa1 mlp / sa2 group / sa2 mlp / sa3 / fp3 / fp2 / fp1 / head
+forward  segment_cloud as one call, and the peak of
+         torch.cuda.max_memory_allocated above what was allocated before it
+decode   decode_waypoints on that head, beside the same steps written in torch
+         on the same GPU (argmax, boolean masks, masked means, the gather of
+         each set's first index, the normalisation; no Euler angles)
+
+Per entry: ms as the median of --runs timed runs after a warm-up, with the
+fastest and slowest run.  Prints one JSON line; --out writes it to a file.
+
+usage: python scripts/bench_policy.py [--batches 64 256] [--runs 7] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "panda-lang-manip_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+N = 5000
+
+
+def stats(ms):
+    return {"ms": round(statistics.median(ms), 3), "spread_ms": [round(min(ms), 3), round(max(ms), 3)]}
+
+
+def timed(fn, runs):
+    """Median of `runs` device-event timings of fn() after one warm-up call."""
+    import torch
+
+    fn()
+    ms = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        keep = fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+        del keep
+    return stats(ms)
+
+
+def staged_forward(sim, net, points, colors, seed, marks):
+    """segment_cloud's wiring with an event recorded after every stage."""
+    import torch
+
+    def mark(name):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        marks.append((name, e))
+
+    B = points.shape[0]
+    mark("start")
+    g1 = sim.group_cloud(points, None, net.SA1_NPOINT, net.SA1_RADII, net.SA1_NSAMPLES, seed, True)
+    l0 = torch.cat([g1.xyz, colors], dim=2)
+    mark("sa1_group")
+    l1 = sim.abstract_features(g1, l0, mlps=net.sa1)
+    mark("sa1_mlp")
+    g2 = sim.group_cloud(g1.new_xyz, None, net.SA2_NPOINT, net.SA2_RADII, net.SA2_NSAMPLES, seed + 1, False)
+    mark("sa2_group")
+    l2 = sim.abstract_features(g2, l1, mlps=net.sa2)
+    mark("sa2_mlp")
+    l3 = sim.shared_mlp(torch.cat([g2.new_xyz, l2], dim=2), net.sa3, pool=net.SA2_NPOINT)
+    mark("sa3")
+    l2 = sim.shared_mlp(sim.propagate_features(g2.new_xyz, torch.zeros(B, 1, 3, device=points.device), l3, l2), net.fp3)
+    mark("fp3")
+    l1 = sim.shared_mlp(sim.propagate_features(g1.new_xyz, g2.new_xyz, l2, l1), net.fp2)
+    mark("fp2")
+    l0 = sim.shared_mlp(sim.propagate_features(g1.xyz, g1.new_xyz, l1, torch.cat([g1.xyz, l0], dim=2)), net.fp1)
+    mark("fp1")
+    head = sim.shared_mlp(l0, net.head)
+    mark("head")
+    return head
+
+
+def torch_decode(head, xyz, centroid, scale, nc):
+    """Inference.predict's lines 68-107 for B clouds in torch ops."""
+    import torch
+
+    B, n = head.shape[:2]
+    labels = head[..., :nc].argmax(-1)
+    outs = []
+    for k, classes in enumerate(((1, 3), (2, 3))):
+        member = (labels == classes[0]) | (labels == classes[1])
+        count = member.sum(1)
+        diff = (xyz - head[..., nc + 3 * k:nc + 3 * k + 3]).double() * member[..., None]
+        way = diff.sum(1) / count[:, None] * scale[:, None].double() + centroid.double()
+        first = torch.where(member, torch.arange(n, device=head.device)[None], n).min(1)[0].clamp(max=n - 1)
+        q = head[torch.arange(B, device=head.device), first, nc + 6 + 4 * k:nc + 10 + 4 * k]
+        outs.append((way.float(), q / q.norm(dim=1, keepdim=True), count, first))
+    return outs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="*", default=[64, 256])
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+
+    from net_helpers import STATE_SEED, seeded_state
+    from pandasim import CloudSegNet
+    from pandasim.sim import PandaSim
+
+    out = {"metric": "ms per batch of clouds of 5 000 points: the stages of segment_cloud, the whole forward with "
+                     "its peak memory above the inputs, decode_waypoints beside the same steps in torch",
+           "runs": a.runs, "device": torch.cuda.get_device_name(0), "N": N, "rows": []}
+    net = CloudSegNet(seeded_state(STATE_SEED), "cuda")
+    for B in a.batches:
+        sim = PandaSim("reach", num_envs=B, device="cuda:0")
+        g = torch.Generator(device="cuda")
+        g.manual_seed(B)
+        points = (torch.rand(B, N, 3, device="cuda", generator=g) - 0.5) * torch.tensor([0.7, 0.7, 0.3], device="cuda")
+        colors = torch.rand(B, N, 3, device="cuda", generator=g)
+        row = {"batch": B}
+        try:
+            staged_forward(sim, net, points, colors, 0, [])  # warm-up
+            per_stage = {}
+            for _ in range(a.runs):
+                marks = []
+                staged_forward(sim, net, points, colors, 0, marks)
+                marks[-1][1].synchronize()
+                for (_, e0), (name, e1) in zip(marks, marks[1:]):
+                    per_stage.setdefault(name, []).append(e0.elapsed_time(e1))
+            row["stages"] = {k: stats(v) for k, v in per_stage.items()}
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            row["forward"] = timed(lambda: sim.segment_cloud(net, points, colors, 0), a.runs)
+            row["forward"]["peak_bytes_above_inputs"] = int(torch.cuda.max_memory_allocated() - base)
+            head, g1 = sim.segment_cloud(net, points, colors, 0)
+            row["decode"] = timed(lambda: sim.decode_waypoints(head, g1.xyz, net.num_classes, g1.centroid, g1.scale),
+                                  a.runs)
+            row["decode_torch"] = timed(lambda: torch_decode(head, g1.xyz, g1.centroid, g1.scale, net.num_classes),
+                                        a.runs)
+            row["decode_speedup_over_torch"] = round(row["decode_torch"]["ms"] / max(row["decode"]["ms"], 1e-6), 2)
+            mine = sim.decode_waypoints(head, g1.xyz, net.num_classes, g1.centroid, g1.scale)
+            ref = torch_decode(head, g1.xyz, g1.centroid, g1.scale, net.num_classes)
+            row["counts_equal_torch"] = bool(all(torch.equal(mine.counts[:, k].long(), ref[k][2]) for k in range(2)))
+            row["head_bytes"] = head.numel() * 4
+            del head, g1, mine, ref
+        except torch.OutOfMemoryError as e:
+            row["error"] = "out of memory: " + str(e).splitlines()[0]
+        out["rows"].append(row)
+        del sim
+        torch.cuda.empty_cache()
+    line = json.dumps(out)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()

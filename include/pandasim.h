@@ -701,6 +701,66 @@ int ps_cloud_decode_waypoints(ps_ctx *ctx, const float *head, int N, int ld, int
                               float *waypoints, float *quats, float *euler_deg, int32_t *counts, int32_t *labels,
                               int32_t *first_idx, void *stream);
 
+/* --- Point-cloud policy: keypoint conditioning --- */
+
+/* The fourth feature channel of the reference's inp_dim = 7 policies
+ * (run_policy.py:202-285, take_rgbd: pix2pix_neighborhood, deproject,
+ * point2point_neighborhood), with the colours, as the feature rows the network
+ * takes -- for the context's B clouds in one launch, without a depth image or
+ * any per-pixel array.
+ *
+ * Inputs.  state, vis and target_poses (device [B, 2, 7] f32 or NULL) as
+ * ps_point_cloud takes them; view: HOST, the keypoint view; keypoints
+ * [B, n_kp, 2] i32 device, (column, row) in that view; radius in pixels;
+ * threshold in metres; values [n_kp] f32 HOST; points [B, K, 3] f32 device;
+ * colors [B, K, 3] u8 device or NULL; count [B] i32 device or NULL.
+ *
+ *   Patch.     The integer offsets (dx, dy) with dx^2 + dy^2 <= radius^2, slot
+ *              order dx ascending, then dy ascending; P is their number (1, 29
+ *              and 197 for radius 0, 3 and 8).  Slot s of keypoint k is pixel
+ *              (column + dx, row + dy).  A slot whose pixel lies outside the
+ *              image is skipped, so a keypoint whose whole disc lies outside
+ *              marks nothing; and every slot of a keypoint with a negative
+ *              coordinate is skipped, whatever the radius: that is how a
+ *              caller says "absent" without a host synchronisation.
+ *   Target.    The world point of an in-image slot: ps_deproject_pixels of that
+ *              pixel on ps_render's depth of the view, bit for bit (the pixel's
+ *              ray is cast inside the kernel), f64.  No depth or workspace
+ *              filter, as PyBullet.deproject has none: a background pixel
+ *              gives its point on the far plane.
+ *   Distance.  With p the f32 point widened to f64 and t a target,
+ *              d2 = (dx*dx + dy*dy) + dz*dz of the f64 differences, every
+ *              operation rounded (no fused multiply-add).  m_k is the least d2
+ *              over keypoint k's in-image slots (a d2 that is NaN never lowers
+ *              it; +inf with no slot).  Keypoint k marks the point iff
+ *              sqrt(m_k) < threshold, strictly and in f64.
+ *   Value.     values[k] of the highest-index keypoint that marks the point,
+ *              else 0.0f: a later keypoint overwrites an earlier one.
+ *   Empty.     With count given, an env whose count is 0 (ps_point_cloud's
+ *              empty cloud) gets all-zero feature rows.
+ *
+ * Outputs.  feats [B, K, ld] f32: with colors, columns out_offset ..
+ * out_offset + 2 take the colour bytes as floats (0..255, exact) and column
+ * out_offset + 3 the value; without, column out_offset takes the value.  Other
+ * columns are left.  targets [B, n_kp, P, 3] f64 or NULL: every slot's target,
+ * NaN for a slot outside the image.
+ *
+ * Limits (PS_ERR_ARG, nothing launched, outputs untouched): a NULL ctx, state,
+ * view, vis, keypoints, values, points or feats, n_kp outside
+ * 1..PS_CLOUD_KEYPOINT_MAX, radius outside 0..PS_CLOUD_KEYPOINT_MAX_RADIUS, a
+ * threshold that is not positive and finite, an empty image or one of 2^31
+ * pixels or more, K outside 1..PS_CLOUD_MAX_DENSE_POINTS, out_offset < 0, the
+ * written columns beyond ld, ld above PS_CLOUD_KEYPOINT_MAX_LD. */
+#define PS_CLOUD_KEYPOINT_MAX 4
+#define PS_CLOUD_KEYPOINT_MAX_RADIUS 8 /* 4 * 197 targets of 24 B in LDS */
+#define PS_CLOUD_KEYPOINT_MAX_LD 4096
+
+int ps_cloud_keypoint_features(ps_ctx *ctx, const void *state, const ps_cloud_view *view, int width, int height,
+                               const ps_visual *vis, const float *target_poses, const int32_t *keypoints, int n_kp,
+                               int radius, double threshold, const float *values, const float *points,
+                               const uint8_t *colors, const int32_t *count, int K, float *feats, int ld,
+                               int out_offset, double *targets, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

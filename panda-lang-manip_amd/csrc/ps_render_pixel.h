@@ -4,8 +4,9 @@
 // observation (cloud_kernels.hip).  The camera of a view/projection pair
 // (Cam, cam_of), the scene a ray is cast into (RenderArgs, render_args_of),
 // the arm primitives' row culling (arm_prim_meets_tile), one pixel's ray cast
-// (render_pixel), its 8-bit colour (colour_u8) and render()'s deprojection of
-// one depth sample (Tran, pix_to_world, deproject_pixel).
+// (render_pixel), its 8-bit colour (colour_u8), render()'s deprojection of
+// one depth sample (Tran, pix_to_world, deproject_pixel) and deproject()'s of
+// one pixel of a list (deproject_at).
 //
 // Every kernel inlines the same bodies; the point-cloud tests hold the fused
 // kernels to ps_render + ps_deproject_image of the same build bit for bit, so
@@ -243,6 +244,18 @@ PS_D bool deproject_pixel(const Tran &T, int width, int height, int r, int c, fl
     double zn = opaque(__dmul_rn(2.0, z)) - 1.0;
     pix_to_world(T, x, y, zn, p);
     return z < 0.99 && p[2] > 0.0 && p[2] < 0.67 && p[0] > -0.5 && p[0] < 0.2;
+}
+
+// PyBullet.deproject of one pixel (pybullet.py:109-146): column pc, row prow
+// inside the image and its window depth -> the world point.  x = px * 1 / w
+// (integer numerator, true division), x *= 2, x -= 1; the same for (h - py);
+// z = 2 depth - 1.  Pixel centres and no filter, unlike deproject_pixel.
+PS_D void deproject_at(const Tran &T, int width, int height, int pc, int prow, float depth, double p[3]) {
+#pragma clang fp contract(off)
+    double x = opaque(opaque((double)pc / (double)width) * 2.0) - 1.0;
+    double y = opaque(opaque((double)(height - prow) / (double)height) * 2.0) - 1.0;
+    double z = opaque(2.0 * (double)depth) - 1.0;
+    pix_to_world(T, x, y, z, p);
 }
 
 }  // namespace

@@ -175,13 +175,8 @@ __global__ __launch_bounds__(256) void k_deproject_pixels(int64_t n_env, int n, 
         points[g * 3 + 0] = points[g * 3 + 1] = points[g * 3 + 2] = __builtin_nan("");
         return;
     }
-    // x = px * 1 / w (integer numerator, true division), x *= 2, x -= 1; the same for
-    // (h - py); z = 2 depth[py, px] - 1
-    double x = opaque(opaque((double)pc / (double)width) * 2.0) - 1.0;
-    double y = opaque(opaque((double)(height - prow) / (double)height) * 2.0) - 1.0;
-    double z = opaque(2.0 * (double)depth[env * (int64_t)width * height + (int64_t)prow * width + pc]) - 1.0;
     double p[3];
-    pix_to_world(T, x, y, z, p);
+    deproject_at(T, width, height, pc, prow, depth[env * (int64_t)width * height + (int64_t)prow * width + pc], p);
     points[g * 3 + 0] = p[0];
     points[g * 3 + 1] = p[1];
     points[g * 3 + 2] = p[2];

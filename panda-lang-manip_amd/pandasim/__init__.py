@@ -10,10 +10,10 @@ from .envs import REGISTRY, PandaVecEnv, make
 from .panda_tasks import (PandaFlipEnv, PandaPickAndPlaceEnv, PandaPushEnv, PandaReachEnv, PandaSlideEnv,
                           PandaStackEnv)
 from .robots import Panda
-from .sim import GRASP_VIEWS, PandaSim
+from .sim import GRASP_VIEWS, PandaSim, keypoint_features_args, patch_size, project_to_pixels
 from .tasks import Flip, PickAndPlace, Push, Reach, Slide, Stack
 
-__all__ = ["make", "PandaVecEnv", "PandaSim", "GRASP_VIEWS", "CloudMlp", "fold_batchnorm", "CloudSegNet", "DecodedWaypoints", "REGISTRY", "PandasimError", "lib", "PyBulletRobot",
+__all__ = ["make", "PandaVecEnv", "PandaSim", "GRASP_VIEWS", "keypoint_features_args", "patch_size", "project_to_pixels", "CloudMlp", "fold_batchnorm", "CloudSegNet", "DecodedWaypoints", "REGISTRY", "PandasimError", "lib", "PyBulletRobot",
            "Task", "RobotTaskEnv", "TimeLimit", "Panda", "Reach", "Push", "PickAndPlace", "PandaReachEnv",
            "PandaPushEnv", "PandaPickAndPlaceEnv", "Slide", "Stack", "Flip", "PandaSlideEnv", "PandaStackEnv", "PandaFlipEnv", "panda_cartesian"]
 __version__ = "0.1.0"

@@ -94,7 +94,8 @@ F, D = P(C.c_float), P(C.c_double)
 # front end of that observation (PandaSim.group_cloud), "propagate" its
 # feature propagation (PandaSim.propagate_features), "mlp" the shared MLP with
 # max-pool (PandaSim.shared_mlp / abstract_features), "decode" the policy's
-# waypoint decoding (PandaSim.decode_waypoints).
+# waypoint decoding (PandaSim.decode_waypoints), "keypoint" the keypoint
+# conditioning of the cloud's feature rows (PandaSim.keypoint_features).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -147,6 +148,8 @@ SIGNATURES = {
     "ps_cloud_mlp": ([V, V, I, I, P(CloudMlpLayer), I, I, V, I64, I, V], I, "mlp"),
     "ps_cloud_group_mlp": ([V, V, V, I, I, V, I, V, I, P(CloudMlpLayer), I, V, I64, I, V], I, "mlp"),
     "ps_cloud_decode_waypoints": ([V, V, I, I, I, V, V, V, C.c_uint32, C.c_uint32, V, V, V, V, V, V, V], I, "decode"),
+    "ps_cloud_keypoint_features": ([V, V, P(CloudView), I, I, P(Visual), V, V, I, I, C.c_double, F, V, V, V, I, V, I, I, V,
+                                    V], I, "keypoint"),
 }
 ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
 MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
@@ -155,11 +158,13 @@ GROUP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "group")
 PROPAGATE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "propagate")
 MLP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "mlp")
 DECODE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "decode")
+KEYPOINT_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "keypoint")
 CLOUD_MAX_VIEWS = 8
 CLOUD_MAX_POINTS, CLOUD_MAX_SCALES, CLOUD_MAX_FEATURES = 8192, 4, 16
 CLOUD_MAX_PROP_FEATURES, CLOUD_MAX_DENSE_POINTS = 2048, 1 << 20
 CLOUD_MLP_MAX_LAYERS, CLOUD_MLP_MAX_HIDDEN, CLOUD_MLP_MAX_LAST = 4, 512, 1024
 CLOUD_DECODE_MAX_CLASSES, CLOUD_DECODE_MAX_LD = 16, 4096
+CLOUD_KEYPOINT_MAX, CLOUD_KEYPOINT_MAX_RADIUS, CLOUD_KEYPOINT_MAX_LD = 4, 8, 4096
 
 
 def exported_symbols():

@@ -15,7 +15,8 @@ the fused multi-view point-cloud observation (cloud_kernels.hip), the
 PointNet++ front end of that observation (group_kernels.hip), its feature
 propagation (propagate_kernels.hip), the shared MLP with max-pool on the f32
 matrix cores (mlp_kernels.hip), the policy's waypoint decoding
-(decode_kernels.hip).
+(decode_kernels.hip), the keypoint conditioning of the cloud's feature rows
+(keypoint_kernels.hip).
 
 Every object is compiled with the same flags (-O3, no -mllvm scheduler
 options).  Round 3 built the group kernels at -O1 after an -O2/-O3 miscompute
@@ -87,7 +88,8 @@ UNITS = ([("pandasim", "pandasim.hip", [])]
          + [("state_kernels", "state_kernels.hip", []), ("plan_kernels", "plan_kernels.hip", []),
             ("render_kernels", "render_kernels.hip", []), ("cloud_kernels", "cloud_kernels.hip", []),
             ("group_kernels", "group_kernels.hip", []), ("propagate_kernels", "propagate_kernels.hip", []),
-            ("mlp_kernels", "mlp_kernels.hip", []), ("decode_kernels", "decode_kernels.hip", [])])
+            ("mlp_kernels", "mlp_kernels.hip", []), ("decode_kernels", "decode_kernels.hip", []),
+            ("keypoint_kernels", "keypoint_kernels.hip", [])])
 
 # diagnostic variants (never loaded by the product unless PANDASIM_LIB names them)
 VARIANTS = {"": [], "prof": ["-DPS_PROFILE_PHASES"]}

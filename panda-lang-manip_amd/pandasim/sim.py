@@ -475,6 +475,94 @@ class PandaSim(CloudNet):
                    _ptr(out["count"]), _ptr(ws), self._stream())
         return out
 
+    def _cloud_view(self, width: int, height: int, view) -> L.CloudView:
+        cv = L.CloudView()
+        vm, pm, tran = self.get_cam2world_transforms(width, height, **dict(view))
+        cv.view[:], cv.proj[:], cv.tran_pix_world[:] = vm, pm, tran.reshape(-1).tolist()
+        return cv
+
+    def keypoint_features(self, points, keypoints, view, colors=None, count=None, radius: int = 3,
+                          threshold: float = 0.1, values=None, width: int = 480, height: int = 480,
+                          return_targets: bool = False):
+        """The keypoint conditioning of the reference's inp_dim = 7 policies
+        (run_policy.py:202-285, take_rgbd) -- fused (ps_cloud_keypoint_features),
+        for every env, without rendering the keypoint view: per keypoint the
+        pixels within `radius` of it (pix2pix_neighborhood, clipped to the
+        image), their world points (deproject), and a cloud point is marked
+        when the nearest of them is closer than `threshold`
+        (point2point_neighborhood).  The channel is values[k] of the last
+        keypoint that marks the point, else 0: the reference's 1.0 for the
+        start keypoint, then 2.0 for the end keypoint.
+
+        points [B, K, 3] f32 and colors None or [B, K, 3] u8 (point_cloud()'s),
+        keypoints [B, n_kp, 2] or [n_kp, 2] integers (column, row) in `view`
+        (a dict of get_cam2world_transforms' keyword arguments), 1 <= n_kp <= 4;
+        a keypoint whose disc lies outside the image marks nothing, and so does
+        one with a negative coordinate (the way to say "absent").  count None or [B] i32 (point_cloud()'s): an env
+        whose count is 0 gets zero rows.  values defaults to
+        (1.0, 2.0, 3.0, 4.0)[:n_kp].  Returns feats [B, K, 4] f32 (the colours
+        as floats 0..255, then the channel; [B, K, 1] without colours), what
+        segment_cloud takes as `colors` of a seven-channel net; with
+        return_targets also targets [B, n_kp, P, 3] f64, the patches' world
+        points (NaN for a pixel outside the image)."""
+        self._check_image_size(width, height)
+        B, dev = self.num_envs, self.device
+        points = torch.as_tensor(points, device=dev)
+        keypoints = torch.as_tensor(np.asarray(keypoints) if not torch.is_tensor(keypoints) else keypoints, device=dev)
+        if colors is not None:
+            colors = torch.as_tensor(colors, device=dev)
+        if count is not None:
+            count = torch.as_tensor(count, device=dev)
+        K, n_kp, radius, threshold, values = keypoint_features_args(B, points, keypoints, colors, count, radius,
+                                                                    threshold, values)
+        if keypoints.dim() == 2:
+            keypoints = keypoints.unsqueeze(0).expand(B, -1, -1)
+        keypoints = keypoints.to(torch.int32).contiguous()
+        points = points.contiguous()
+        colors = None if colors is None else colors.contiguous()
+        count = None if count is None else count.contiguous()
+        cv = self._cloud_view(width, height, view)
+        ld = 1 if colors is None else 4
+        feats = torch.empty(B, K, ld, dtype=torch.float32, device=dev)
+        targets = (torch.empty(B, n_kp, patch_size(radius), 3, dtype=torch.float64, device=dev)
+                   if return_targets else None)
+        vis = self._visual()
+        poses = self._target_poses().contiguous()
+        self._call("ps_cloud_keypoint_features", self._ctx, _ptr(self.state), C.byref(cv), int(width), int(height),
+                   C.byref(vis), _ptr(poses), _ptr(keypoints), n_kp, radius, threshold, (C.c_float * n_kp)(*values),
+                   _ptr(points), _ptr(colors), _ptr(count), K, _ptr(feats), ld, 0, _ptr(targets), self._stream())
+        return (feats, targets) if return_targets else feats
+
+    def keypoint_cloud(self, keypoints, views=None, keypoint_view=None, n_points: int = 5000, width: int = 480,
+                       height: int = 480, radius: int = 3, threshold: float = 0.1, values=None, seed: int = 0,
+                       crop=None) -> Dict[str, torch.Tensor]:
+        """take_rgbd's observation for every env: point_cloud(views, ...) and
+        keypoint_features of that cloud with its count.  keypoint_view
+        defaults to views[0], the view take_rgbd picks its keypoints in.
+        Returns point_cloud's dict plus feats [B, K, 4] f32 and cond [B, K] f32
+        (the channel alone, a view of feats): predict_waypoints(net, out["points"],
+        out["feats"]) runs a seven-channel CloudSegNet on it."""
+        views = GRASP_VIEWS if views is None else list(views)
+        out = self.point_cloud(views, n_points, width, height, seed, crop)
+        kv = views[0] if keypoint_view is None else keypoint_view
+        out["feats"] = self.keypoint_features(out["points"], keypoints, kv, out["colors"], out["count"], radius,
+                                              threshold, values, width, height)
+        out["cond"] = out["feats"][..., 3]
+        return out
+
+    def project_to_pixels(self, points, width: int = 480, height: int = 480, **view) -> torch.Tensor:
+        """render()'s waypoints_proj for every env, on the device: world points
+        [B, n, 3] (or [n, 3], the same for every env) -> [B, n, 2] i32
+        (column, row) in the view of get_cam2world_transforms(width, height,
+        **view).  How a keypoint is got from an object's position."""
+        vm, pm, _ = self.get_cam2world_transforms(width, height, **view)
+        points = torch.as_tensor(points, device=self.device)
+        if points.dim() == 2:
+            points = points.unsqueeze(0).expand(self.num_envs, -1, -1)
+        if points.dim() != 3 or points.shape[0] != self.num_envs or points.shape[2] != 3:
+            raise ValueError(f"project_to_pixels: points must be [{self.num_envs}, n, 3], got {tuple(points.shape)}")
+        return project_to_pixels(points, vm, pm, width, height)
+
     def deproject(self, depth, pixels, tran_pix_world, width: int = 480, height: int = 480) -> torch.Tensor:
         """PyBullet.deproject (pybullet.py:109-146) per env: depth [B, h, w]
         (or one [h, w] image for every env), pixels [n, 2] or [B, n, 2]
@@ -807,3 +895,73 @@ def quaternion_from_euler(e: torch.Tensor) -> torch.Tensor:
     cr, sr, cp, sp, cy, sy = torch.cos(r), torch.sin(r), torch.cos(p), torch.sin(p), torch.cos(y), torch.sin(y)
     return torch.stack([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy,
                         cr * cp * cy + sr * sp * sy], -1)
+
+
+# ---------------------------------------------- keypoint conditioning (host)
+def patch_size(radius: int) -> int:
+    """P of keypoint_features: the integer offsets within `radius` of a pixel
+    (1, 29 and 197 for radius 0, 3 and 8)."""
+    r = int(radius)
+    return sum(2 * math.isqrt(r * r - dx * dx) + 1 for dx in range(-r, r + 1))
+
+
+def keypoint_features_args(num_envs: int, points, keypoints, colors, count, radius, threshold, values):
+    """keypoint_features' argument checks (ValueError), on tensors of any
+    device: -> K, n_kp, radius, threshold and the values as floats."""
+    from .cloudnet import _want
+
+    B, fn = int(num_envs), "keypoint_features"
+    _want(fn, "points", points, (B, "K", 3))
+    K = int(points.shape[1])
+    if not 1 <= K <= L.CLOUD_MAX_DENSE_POINTS:
+        raise ValueError(f"{fn}: points holds K = {K} points (1 to {L.CLOUD_MAX_DENSE_POINTS})")
+    whole = torch.is_tensor(keypoints) and not keypoints.is_floating_point() and not keypoints.is_complex() \
+        and keypoints.dtype != torch.bool
+    if not whole or keypoints.dim() not in (2, 3) or keypoints.shape[-1] != 2 or \
+            (keypoints.dim() == 3 and keypoints.shape[0] != B):
+        raise ValueError(f"{fn}: keypoints must be [{B}, n_kp, 2] or [n_kp, 2] integers (column, row), got "
+                         f"{tuple(keypoints.shape) if torch.is_tensor(keypoints) else type(keypoints).__name__} "
+                         f"{getattr(keypoints, 'dtype', '')}")
+    n_kp = int(keypoints.shape[-2])
+    if not 1 <= n_kp <= L.CLOUD_KEYPOINT_MAX:
+        raise ValueError(f"{fn}: keypoints holds n_kp = {n_kp} keypoints (1 to {L.CLOUD_KEYPOINT_MAX})")
+    if colors is not None:
+        _want(fn, "colors", colors, (B, K, 3), torch.uint8)
+    if count is not None:
+        _want(fn, "count", count, (B,), torch.int32)
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or \
+            not 0 <= radius <= L.CLOUD_KEYPOINT_MAX_RADIUS:
+        raise ValueError(f"{fn}: radius = {radius!r} (a whole number of pixels from 0 to {L.CLOUD_KEYPOINT_MAX_RADIUS})")
+    try:
+        thr = float(threshold)
+    except (TypeError, ValueError):
+        thr = math.nan
+    if not 0.0 < thr < math.inf:
+        raise ValueError(f"{fn}: threshold = {threshold!r} must be positive and finite")
+    if values is None:
+        values = (1.0, 2.0, 3.0, 4.0)[:n_kp]
+    try:
+        values = [float(v) for v in values]
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: values must be {n_kp} numbers") from None
+    if len(values) != n_kp:
+        raise ValueError(f"{fn}: values holds {len(values)} numbers for n_kp = {n_kp} keypoints")
+    return K, n_kp, int(radius), thr, values
+
+
+def project_to_pixels(points, view_matrix, proj_matrix, width: int, height: int) -> torch.Tensor:
+    """render()'s waypoints_proj arithmetic (pybullet.py:251-258) for a tensor
+    of world points [..., 3] on any device -> [..., 2] i32 (column, row):
+    (x, y, z, w) = P V (p, 1) in f64, x = (x / w + 1) / 2 * width, the same for
+    y with height, and [int(x), int(height - y)], int() truncating towards 0.
+    P V is numpy's product of the order='F' matrices, as there; its product
+    with the point is written out term by term (k ascending)."""
+    PV = np.matmul(np.asarray(proj_matrix).reshape([4, 4], order="F"), np.asarray(view_matrix).reshape([4, 4], order="F"))
+    p = torch.as_tensor(points).to(torch.float64)
+    px, py, pz = p[..., 0], p[..., 1], p[..., 2]
+    x, y, _, w = (px * float(PV[r, 0]) + py * float(PV[r, 1]) + pz * float(PV[r, 2]) + float(PV[r, 3]) for r in range(4))
+    x, y = (x / w + 1) / 2 * width, (y / w + 1) / 2 * height
+    out = torch.stack([x, height - y], -1).trunc()
+    # a point on the camera plane has no pixel: as far off the image as i32 goes
+    return torch.nan_to_num(out, nan=-2.0 ** 31, posinf=2.0 ** 31 - 1, neginf=-2.0 ** 31).clamp(
+        -2.0 ** 31, 2.0 ** 31 - 1).to(torch.int32)

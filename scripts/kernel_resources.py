@@ -93,7 +93,8 @@ def main(argv):
                           glob.glob(os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim",
                                                  "motion_*.o")) +
                           [os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim", n)
-                           for n in ("render_kernels.o", "cloud_kernels.o", "group_kernels.o", "propagate_kernels.o", "mlp_kernels.o")])
+                           for n in ("render_kernels.o", "cloud_kernels.o", "group_kernels.o", "propagate_kernels.o", "mlp_kernels.o", "decode_kernels.o",
+                                     "keypoint_kernels.o")])
     table = {}
     with tempfile.TemporaryDirectory() as tmp:
         for p in paths:

@@ -639,6 +639,53 @@ int ps_cloud_group_mlp(ps_ctx *ctx, const float *xyz, const float *feats, int N,
                        int S, const int32_t *group_idx, int K, const ps_cloud_mlp_layer *layers, int n_layers,
                        float *out, int64_t out_stride, int out_offset, void *stream);
 
+/* --- PointNet++ shared MLP with max-pool, bfloat16 on the matrix cores --- */
+
+/* The same layers at reduced precision: operands rounded to bfloat16, products
+ * and sums in f32 on the bf16 matrix cores (16 times the f32 MFMA's rate).  A
+ * capability beside ps_cloud_mlp / ps_cloud_group_mlp, which are unchanged.
+ *
+ * Per row x [C0] and layer:
+ *   xh[k] = bf16(x[k])                     round to nearest even from f32 (layer 0: the caller's f32
+ *                                          rows; later layers: the previous layer's f32 y after its ReLU)
+ *   Wh    = the layer's weights, bf16, rounded once on the host at upload
+ *   y[o]  = b[o] + sum_k xh[k] * Wh[o][k]  b f32; products exact; accumulated in f32 on the matrix
+ *                                          core, the order of the additions unspecified
+ *   if relu:  y[o] = y[o] > 0 ? y[o] : 0
+ * The last layer's y is written as f32 and is not rounded to bf16.  Pooling
+ * over G rows, out_stride / out_offset, the -inf start of the maximum and the
+ * clamping of the gather's indices are exactly ps_cloud_mlp's and
+ * ps_cloud_group_mlp's.  In the gather variant the row is feats[group_idx]
+ * then xyz[group_idx] - xyz[centre_idx]: the subtraction in f32 first, its
+ * result then rounded to bf16.
+ *
+ * Unspecified: the result for an input, weight or bias that is not finite, and
+ * wherever a nonzero operand's bf16 value is subnormal (whether the matrix core
+ * or the conversion flushes it is not promised either way).
+ * Guaranteed: the result is deterministic (the same bits on a repeated call),
+ * and a cloud's bits do not depend on its position in the batch or on the
+ * other clouds.
+ *
+ * A layer's W is [c_out, ldw] bf16 bit patterns (uint16), row-major, with
+ * ldw = c_in rounded up to a multiple of 8 and columns c_in .. ldw-1 zero, at a
+ * 16-byte aligned device address; b is [c_out] f32.  The array of layers is
+ * HOST memory.  Limits and refusals (PS_ERR_ARG, nothing launched, outputs
+ * untouched) are those of the f32 calls, and a W that is not 16-byte aligned. */
+typedef struct {
+    const uint16_t *W; /* [c_out, ldw] bf16 bits, row-major; ldw = c_in rounded up to a multiple of 8,
+                          columns c_in..ldw-1 zero; 16-byte aligned */
+    const float *b;    /* [c_out] f32 */
+    int32_t c_out;
+    int32_t relu;
+} ps_cloud_mlp_bfloat_layer;
+
+int ps_cloud_mlp_bfloat(ps_ctx *ctx, const float *rows, int R, int C0, const ps_cloud_mlp_bfloat_layer *layers,
+                        int n_layers, int G, float *out, int64_t out_stride, int out_offset, void *stream);
+int ps_cloud_group_mlp_bfloat(ps_ctx *ctx, const float *xyz, const float *feats, int N, int D,
+                              const int32_t *centre_idx, int S, const int32_t *group_idx, int K,
+                              const ps_cloud_mlp_bfloat_layer *layers, int n_layers, float *out, int64_t out_stride,
+                              int out_offset, void *stream);
+
 /* --- Point-cloud policy: waypoint decoding --- */
 
 /* What envs/inference/inference_cls_off_rot.py: Inference.predict does after

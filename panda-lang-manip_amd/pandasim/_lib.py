@@ -59,6 +59,12 @@ class CloudMlpLayer(C.Structure):
     _fields_ = [("W", C.c_void_p), ("b", C.c_void_p), ("c_out", C.c_int32), ("relu", C.c_int32)]
 
 
+class CloudMlpBfloatLayer(C.Structure):
+    """ps_cloud_mlp_bfloat_layer: W [c_out, ldw] bf16 bits (ldw = c_in rounded up to
+    a multiple of 8, 16-byte aligned) and b [c_out] f32 (device pointers)."""
+    _fields_ = [("W", C.c_void_p), ("b", C.c_void_p), ("c_out", C.c_int32), ("relu", C.c_int32)]
+
+
 class CloudCrop(C.Structure):
     """ps_cloud_crop: the open box lo < p < hi on the world point."""
     _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
@@ -95,7 +101,9 @@ F, D = P(C.c_float), P(C.c_double)
 # feature propagation (PandaSim.propagate_features), "mlp" the shared MLP with
 # max-pool (PandaSim.shared_mlp / abstract_features), "decode" the policy's
 # waypoint decoding (PandaSim.decode_waypoints), "keypoint" the keypoint
-# conditioning of the cloud's feature rows (PandaSim.keypoint_features).
+# conditioning of the cloud's feature rows (PandaSim.keypoint_features),
+# "bfloat" the shared MLP's learned layers in reduced precision (bfloat16 operands
+# on the bf16 matrix cores: CloudMlp(..., precision="bfloat16")).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -147,6 +155,8 @@ SIGNATURES = {
     "ps_cloud_feature_propagation": ([V, V, I, V, I, V, I, V, I, V, V, V, V], I, "propagate"),
     "ps_cloud_mlp": ([V, V, I, I, P(CloudMlpLayer), I, I, V, I64, I, V], I, "mlp"),
     "ps_cloud_group_mlp": ([V, V, V, I, I, V, I, V, I, P(CloudMlpLayer), I, V, I64, I, V], I, "mlp"),
+    "ps_cloud_mlp_bfloat": ([V, V, I, I, P(CloudMlpBfloatLayer), I, I, V, I64, I, V], I, "bfloat"),
+    "ps_cloud_group_mlp_bfloat": ([V, V, V, I, I, V, I, V, I, P(CloudMlpBfloatLayer), I, V, I64, I, V], I, "bfloat"),
     "ps_cloud_decode_waypoints": ([V, V, I, I, I, V, V, V, C.c_uint32, C.c_uint32, V, V, V, V, V, V, V], I, "decode"),
     "ps_cloud_keypoint_features": ([V, V, P(CloudView), I, I, P(Visual), V, V, I, I, C.c_double, F, V, V, V, I, V, I, I, V,
                                     V], I, "keypoint"),
@@ -157,6 +167,7 @@ CLOUD_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "cloud")
 GROUP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "group")
 PROPAGATE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "propagate")
 MLP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "mlp")
+BFLOAT_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "bfloat")
 DECODE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "decode")
 KEYPOINT_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "keypoint")
 CLOUD_MAX_VIEWS = 8

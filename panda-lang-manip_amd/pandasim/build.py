@@ -14,7 +14,8 @@ reward / Euler conversion (state_kernels.hip), the motion plans
 the fused multi-view point-cloud observation (cloud_kernels.hip), the
 PointNet++ front end of that observation (group_kernels.hip), its feature
 propagation (propagate_kernels.hip), the shared MLP with max-pool on the f32
-matrix cores (mlp_kernels.hip), the policy's waypoint decoding
+matrix cores (mlp_kernels.hip) and in bfloat16 on the bf16 ones
+(mlp_bfloat_kernels.hip), the policy's waypoint decoding
 (decode_kernels.hip), the keypoint conditioning of the cloud's feature rows
 (keypoint_kernels.hip).
 
@@ -89,7 +90,8 @@ UNITS = ([("pandasim", "pandasim.hip", [])]
             ("render_kernels", "render_kernels.hip", []), ("cloud_kernels", "cloud_kernels.hip", []),
             ("group_kernels", "group_kernels.hip", []), ("propagate_kernels", "propagate_kernels.hip", []),
             ("mlp_kernels", "mlp_kernels.hip", []), ("decode_kernels", "decode_kernels.hip", []),
-            ("keypoint_kernels", "keypoint_kernels.hip", [])])
+            ("keypoint_kernels", "keypoint_kernels.hip", []),
+            ("mlp_bfloat_kernels", "mlp_bfloat_kernels.hip", [])])
 
 # diagnostic variants (never loaded by the product unless PANDASIM_LIB names them)
 VARIANTS = {"": [], "prof": ["-DPS_PROFILE_PHASES"]}

@@ -97,7 +97,8 @@ class CloudNet:
 
     def shared_mlp(self, rows, layers: "CloudMlp", pool: int = 1, out=None, out_offset: int = 0):
         """The learned layers between the point-cloud steps, at inference
-        (ps_cloud_mlp, f32 MFMA): per row the chain of `layers` (pointwise
+        (ps_cloud_mlp, f32 MFMA; with a CloudMlp of precision "bfloat16"
+        ps_cloud_mlp_bfloat, bf16 MFMA): per row the chain of `layers` (pointwise
         linear layers with the batch norm folded in, ReLU where a layer says
         so), then the maximum over every `pool` consecutive rows -- the loop
         F.relu(bn(conv(x))) and torch.max(x, 2)[0] of pointnet2_utils.py:196-200
@@ -116,8 +117,8 @@ class CloudNet:
         rows = rows.contiguous()
         if out is None:
             out = torch.empty(B, R // pool, width, dtype=torch.float32, device=dev)
-        self._call("ps_cloud_mlp", self._ctx, _ptr(rows), R, C0, layers.array, len(layers), int(pool), _ptr(out),
-                   int(out.shape[2]), int(out_offset), self._stream())
+        self._call("ps_cloud_mlp" + _SUFFIX[_precision_of(layers)], self._ctx, _ptr(rows), R, C0, layers.array,
+                   len(layers), int(pool), _ptr(out), int(out.shape[2]), int(out_offset), self._stream())
         return out
 
     def abstract_features(self, xyz, feats=None, centre_idx=None, group_idx=None, mlps=None, fused=None):
@@ -132,7 +133,10 @@ class CloudNet:
         values bit for bit through a grouped tensor of one scale at a time
         (D <= 16).  The default (None) is the composed path where it exists,
         which measured 1.4 to 2.3 % faster at sa1's shape,
-        and the fused one above D = 16.
+        and the fused one above D = 16.  With mlps of precision "bfloat16"
+        (all of them: a mix raises ValueError) the entry points are
+        ps_cloud_group_mlp_bfloat / ps_cloud_mlp_bfloat, the default is the
+        fused one, and the two paths give the same bits as well.
 
         xyz [B, N, 3] f32, feats None or [B, N, D] f32 (D <= 2048), centre_idx
         [B, S] i32, group_idx a list of [B, S, K_k] i32, mlps a list of
@@ -149,19 +153,20 @@ class CloudNet:
         xyz, centre_idx = xyz.contiguous(), centre_idx.contiguous()
         feats = None if feats is None else feats.contiguous()
         out = torch.empty(B, S, width, dtype=torch.float32, device=dev)
+        suffix = _SUFFIX[_precision_of(mlps[0])]
         if fused is None:
-            fused = D > L.CLOUD_MAX_FEATURES
+            fused = D > L.CLOUD_MAX_FEATURES or suffix != ""
         for gi, mlp, off in zip(group_idx, mlps, offsets):
             gi, K = gi.contiguous(), int(gi.shape[2])
             if fused:
-                self._call("ps_cloud_group_mlp", self._ctx, _ptr(xyz), _ptr(feats), N, D, _ptr(centre_idx), S, _ptr(gi),
+                self._call("ps_cloud_group_mlp" + suffix, self._ctx, _ptr(xyz), _ptr(feats), N, D, _ptr(centre_idx), S, _ptr(gi),
                            K, mlp.array, len(mlp), _ptr(out), width, off, self._stream())
             else:
                 grouped = torch.empty(B, S, K, D + 3, dtype=torch.float32, device=dev)
                 self._call("ps_cloud_group", self._ctx, _ptr(xyz), _ptr(feats), N, D, _ptr(centre_idx), S, _ptr(gi), K,
                            _ptr(grouped), None, self._stream())
-                self._call("ps_cloud_mlp", self._ctx, _ptr(grouped), S * K, D + 3, mlp.array, len(mlp), K, _ptr(out),
-                           width, off, self._stream())
+                self._call("ps_cloud_mlp" + suffix, self._ctx, _ptr(grouped), S * K, D + 3, mlp.array, len(mlp), K,
+                           _ptr(out), width, off, self._stream())
         return out
 
     def decode_waypoints(self, head, xyz, num_classes: int, centroid=None, scale=None, start_classes=(1, 3),
@@ -392,20 +397,72 @@ def cloud_mlp_layers(layers):
     return out
 
 
+PRECISIONS = ("float32", "bfloat16")
+_SUFFIX = {"float32": "", "bfloat16": "_bfloat"}  # of the library's entry points
+
+
+def _check_precision(what: str, precision) -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"{what}: precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
+
+
+def round_bfloat16(a):
+    """f32 -> bfloat16, round to nearest even on the f32 bit pattern (host
+    numpy): -> (the bf16 bit patterns as uint16, their values as float32), in
+    a's shape.  A value beyond the largest finite bf16 by half a step or more
+    rounds to infinity; NaN stays NaN."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    u = a.view(np.uint32)
+    r = ((u.astype(np.uint64) + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    nan = np.isnan(a)
+    if nan.any():  # the carry must not turn a NaN into an infinity or a number
+        r = np.where(nan, ((u >> 16) | 0x40).astype(np.uint16), r)
+    return r, (r.astype(np.uint32) << 16).view(np.float32)
+
+
+def pack_bfloat16(w):
+    """W [c_out, c_in] f32 -> [c_out, ldw] uint16: its bf16 bit patterns with
+    ldw = c_in rounded up to a multiple of 8 and zeros behind c_in (the layout
+    of ps_cloud_mlp_bfloat_layer.W)."""
+    c_out, c_in = w.shape
+    out = np.zeros((c_out, (c_in + 7) & ~7), np.uint16)
+    out[:, :c_in] = round_bfloat16(w)[0]
+    return out
+
+
 class CloudMlp:
     """The layers of one shared MLP (PandaSim.shared_mlp, abstract_features):
     a sequence of (W [c_out, c_in] f32, b [c_out] f32, relu), uploaded once to
     `device` and kept alive here.  c_in is the first layer's input width,
-    widths the layers' outputs; array / len() are what the library takes."""
+    widths the layers' outputs; array / len() are what the library takes.
+    precision "float32" (the default) uploads W as it is; "bfloat16" rounds W
+    to bfloat16 once here (pack_bfloat16; a weight that rounds to infinity
+    raises ValueError) and keeps b f32: W is then the uint16 tensor, array the
+    bfloat layer struct, and the calls go to the bf16 matrix cores."""
 
-    def __init__(self, layers, device="cuda"):
+    def __init__(self, layers, device="cuda", precision="float32"):
+        self.precision = _check_precision("CloudMlp", precision)
         host = cloud_mlp_layers(layers)
         self.c_in = int(host[0][0].shape[1])
         self.widths = [int(w.shape[0]) for w, _, _ in host]
         self.relu = [r for _, _, r in host]
         self.device = torch.device(device)
-        self.W = [torch.from_numpy(w).to(self.device) for w, _, _ in host]
         self.b = [torch.from_numpy(b).to(self.device) for _, b, _ in host]
+        if precision == "bfloat16":
+            packed = [pack_bfloat16(w) for w, _, _ in host]
+            for k, p in enumerate(packed):
+                if ((p & 0x7FFF) == 0x7F80).any():
+                    raise ValueError(f"CloudMlp: layer {k} has a weight that rounds to infinity in bfloat16")
+            # int16 storage of the same bits: torch has no uint16 arithmetic, and needs none here
+            self.W = [torch.from_numpy(p.view(np.int16)).to(self.device) for p in packed]
+            if any(w.data_ptr() % 16 for w in self.W):
+                raise ValueError("CloudMlp: the device allocator returned a W that is not 16-byte aligned")
+            self.array = (L.CloudMlpBfloatLayer * len(host))()
+            for a, w, b, r in zip(self.array, self.W, self.b, self.relu):
+                a.W, a.b, a.c_out, a.relu = w.data_ptr(), b.data_ptr(), int(w.shape[0]), int(r)
+            return
+        self.W = [torch.from_numpy(w).to(self.device) for w, _, _ in host]
         self.array = (L.CloudMlpLayer * len(host))()
         for a, w, b, r in zip(self.array, self.W, self.b, self.relu):
             a.W, a.b, a.c_out, a.relu = w.data_ptr(), b.data_ptr(), int(w.shape[0]), int(r)
@@ -418,6 +475,11 @@ def _mlp_of(what: str, layers):
     if not (hasattr(layers, "widths") and hasattr(layers, "c_in") and hasattr(layers, "array")):
         raise ValueError(f"{what}: layers must be a CloudMlp, got {type(layers).__name__}")
     return layers
+
+
+def _precision_of(layers) -> str:
+    """A CloudMlp's precision; an object without one is a float32 one."""
+    return getattr(layers, "precision", "float32")
 
 
 def shared_mlp_args(num_envs: int, rows, layers, pool, out, out_offset):
@@ -477,6 +539,9 @@ def abstract_features_args(num_envs: int, xyz, feats, centre_idx, group_idx, mlp
             raise ValueError(f"abstract_features: group_idx[{k}] has K = 0 neighbours (at least 1)")
         if mlp.c_in != D + 3:
             raise ValueError(f"abstract_features: mlps[{k}] takes {mlp.c_in} channels, the rows have D + 3 = {D + 3}")
+        if _precision_of(mlp) != _precision_of(mlps[0]):
+            raise ValueError(f"abstract_features: mlps[{k}] is {_precision_of(mlp)}, mlps[0] {_precision_of(mlps[0])} "
+                             f"(one precision for all scales)")
         offsets.append(width)
         width += mlp.widths[-1]
     return N, S, D, offsets, width
@@ -623,18 +688,21 @@ class CloudSegNet:
     conv2 without (dropout is the identity at inference).  num_classes,
     num_input_channels and every width come from the shapes; a missing or
     mis-shaped key raises ValueError naming it.  The sampling constants are the
-    reference's (model_cls_off_rot.py:12-14)."""
+    reference's (model_cls_off_rot.py:12-14).  `precision` ("float32" or
+    "bfloat16") is that of every CloudMlp of the net; sampling, grouping,
+    propagation and decoding are f32 either way."""
 
     SA1_NPOINT, SA1_RADII, SA1_NSAMPLES = 512, (0.1, 0.2, 0.4), (32, 64, 128)
     SA2_NPOINT, SA2_RADII, SA2_NSAMPLES = 128, (0.4, 0.8), (64, 128)
     NUM_OUTPUT_CHANNELS = 14  # two offsets and two quaternions behind the logits
 
-    def __init__(self, state, device="cuda", eps: float = 1e-5):
+    def __init__(self, state, device="cuda", eps: float = 1e-5, precision="float32"):
+        self.precision = _check_precision("CloudSegNet", precision)
         layers, self.num_classes, self.num_input_channels = segnet_layers(state, eps)
         self.device = torch.device(device)
-        self.sa1 = [CloudMlp(mlp, self.device) for mlp in layers["sa1"]]
-        self.sa2 = [CloudMlp(mlp, self.device) for mlp in layers["sa2"]]
-        self.sa3, self.fp3, self.fp2, self.fp1, self.head = (CloudMlp(layers[n], self.device)
+        self.sa1 = [CloudMlp(mlp, self.device, precision) for mlp in layers["sa1"]]
+        self.sa2 = [CloudMlp(mlp, self.device, precision) for mlp in layers["sa2"]]
+        self.sa3, self.fp3, self.fp2, self.fp1, self.head = (CloudMlp(layers[n], self.device, precision)
                                                              for n in ("sa3", "fp3", "fp2", "fp1", "head"))
         self.widths = {n: [m.widths for m in v] if isinstance(v, list) else v.widths
                        for n, v in (("sa1", self.sa1), ("sa2", self.sa2), ("sa3", self.sa3), ("fp3", self.fp3),

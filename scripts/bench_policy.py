@@ -13,9 +13,14 @@ decode   decode_waypoints on that head, beside the same steps written in torch
          each set's first index, the normalisation; no Euler angles)
 
 Per entry: ms as the median of --runs timed runs after a warm-up, with the
-fastest and slowest run.  Prints one JSON line; --out writes it to a file.
+fastest and slowest run.  --precision float32 bfloat16 gives one row per batch
+and precision of the net's learned layers (CloudSegNet(..., precision=...)) in
+the same session, and for bfloat16 the accuracy of its head against the f32
+net's on the same clouds: max |head difference|, the share of equal labels and
+the distance between the decoded waypoints.  Prints one JSON line; --out
+writes it to a file.
 
-usage: python scripts/bench_policy.py [--batches 64 256] [--runs 7] [--out FILE]
+usage: python scripts/bench_policy.py [--batches 64 256] [--precision float32 bfloat16] [--runs 7] [--out FILE]
 """
 import argparse
 import json
@@ -106,6 +111,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="*", default=[64, 256])
     ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--precision", nargs="*", default=["float32"], choices=["float32", "bfloat16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -117,14 +123,15 @@ def main():
     out = {"metric": "ms per batch of clouds of 5 000 points: the stages of segment_cloud, the whole forward with "
                      "its peak memory above the inputs, decode_waypoints beside the same steps in torch",
            "runs": a.runs, "device": torch.cuda.get_device_name(0), "N": N, "rows": []}
-    net = CloudSegNet(seeded_state(STATE_SEED), "cuda")
-    for B in a.batches:
+    nets = {p: CloudSegNet(seeded_state(STATE_SEED), "cuda", precision=p) for p in a.precision}
+    for B, precision in ((B, p) for B in a.batches for p in a.precision):
+        net = nets[precision]
         sim = PandaSim("reach", num_envs=B, device="cuda:0")
         g = torch.Generator(device="cuda")
         g.manual_seed(B)
         points = (torch.rand(B, N, 3, device="cuda", generator=g) - 0.5) * torch.tensor([0.7, 0.7, 0.3], device="cuda")
         colors = torch.rand(B, N, 3, device="cuda", generator=g)
-        row = {"batch": B}
+        row = {"batch": B, "precision": precision}
         try:
             staged_forward(sim, net, points, colors, 0, [])  # warm-up
             per_stage = {}
@@ -151,6 +158,22 @@ def main():
             ref = torch_decode(head, g1.xyz, g1.centroid, g1.scale, net.num_classes)
             row["counts_equal_torch"] = bool(all(torch.equal(mine.counts[:, k].long(), ref[k][2]) for k in range(2)))
             row["head_bytes"] = head.numel() * 4
+            if precision != "float32":
+                from pandasim import CloudSegNet as Net
+
+                f32 = nets.get("float32") or Net(seeded_state(STATE_SEED), "cuda")
+                head32, _ = sim.segment_cloud(f32, points, colors, 0)
+                ref32 = sim.decode_waypoints(head32, g1.xyz, net.num_classes, g1.centroid, g1.scale, return_labels=True)
+                lab = sim.decode_waypoints(head, g1.xyz, net.num_classes, g1.centroid, g1.scale, return_labels=True)
+                dist = (lab.waypoints - ref32.waypoints).norm(dim=-1)
+                both = torch.isfinite(dist)
+                row["against_float32"] = {
+                    "max_abs_head_difference": float((head - head32).abs().max()),
+                    "max_abs_head": float(head32.abs().max()),
+                    "share_of_equal_labels": float((lab.labels == ref32.labels).float().mean()),
+                    "waypoint_distance_m_max": float(dist[both].max()) if bool(both.any()) else None,
+                    "waypoint_sets_compared": int(both.sum())}
+                del head32, ref32, lab
             del head, g1, mine, ref
         except torch.OutOfMemoryError as e:
             row["error"] = "out of memory: " + str(e).splitlines()[0]

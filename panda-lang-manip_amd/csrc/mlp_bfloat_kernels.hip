@@ -1,18 +1,19 @@
 // mlp_bfloat_kernels.hip — the shared MLP of the PointNet++ models at inference
 // in reduced precision (include/pandasim.h, "bfloat16 on the matrix cores"):
 // the layers of mlp_kernels.hip with operands rounded to bfloat16 and f32
-// accumulation, on v_mfma_f32_32x32x16_bf16.  A capability beside the f32
-// kernel, which is untouched.
+// accumulation, on v_mfma_f32_32x32x16_bf16.  The tile, its rows' sources, the
+// layers' buffers and the host side are ps_mlp_tile.h's, one text for this
+// kernel and the f32 one; this file has what bfloat16 changes and the kernel
+// body (the layer select and the last layer's epilogue
+// measured slower as shared functions, so each file has its own).
 //
 // One kernel, k_cloud_mlp_bfloat<GATHER>: a workgroup of 1, 2, 4 or 8 waves
-// owns a tile of 64 rows.  The tile's activations stay in LDS from the first
-// layer to the last as bf16 ([row][channel], two buffers the layers alternate
-// between); the waves share the rows and split a layer's output channels in
-// chunks of 32, so a wave carries two accumulators (rows 0..31 and 32..63 of
-// the tile) that share every weight fragment.  An MFMA operand fragment is 8
-// consecutive k of one row: one 128-bit LDS read of the activations, one
-// 128-bit global read of the weights (W is [c_out, ldw] bf16 with ldw a
-// multiple of 8 and 16-byte aligned, so the weights need no staging).
+// owns a tile of 64 rows, kept in LDS as bf16, so a wave carries two
+// accumulators (rows 0..31 and 32..63 of the tile) that share every weight
+// fragment.  An MFMA operand fragment is 8 consecutive k of one row: one
+// 128-bit LDS read of the activations, one 128-bit global read of the weights
+// (W is [c_out, ldw] bf16 with ldw a multiple of 8 and 16-byte aligned, so the
+// weights need no staging).
 //
 // A hidden layer is computed transposed, D = W x^T: a lane then holds four
 // consecutive channels of its own tile row in every four accumulator
@@ -21,51 +22,24 @@
 // rows in the registers and the channel on the lane as in the f32 kernel, so
 // the pooled maximum is taken in registers and `out` is written along the
 // channels.  The bias is the initial accumulator in both.  A first layer
-// wider than kBfKChunk is streamed through LDS in chunks of k with the
-// accumulators kept.  A group longer than a tile is walked tile by tile by one
-// workgroup with the running maximum in LDS.  No atomics, no scratch.
+// wider than kMlpKChunk is streamed through LDS in chunks of k with the
+// accumulators kept.  No atomics, no scratch.
 //
 // LDS rows have a pitch of (a multiple of 32) + 8 bf16: 16 bytes times an odd
 // number, so the 16 rows that a ds_read_b128 lane group reads at one column
 // fall on 16 different 16-byte slots of the 256-byte bank row.
-#include "ps_cloud_math.h"
+#include "ps_mlp_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kBfRows = 64;       // rows of a tile: two MFMA row blocks
-constexpr int kBfChunk = 32;      // output channels of one wave's pass: the MFMA's N
 constexpr int kBfMaxWaves = 8;
-constexpr int kBfKChunk = 512;    // most input channels resident in LDS (= the hidden limit)
 constexpr int kBfKStep = 16;      // k of one MFMA
 constexpr int kBfPad = 8;         // bf16 past a row's channels
-constexpr int kBfMaxHidden = PS_CLOUD_MLP_MAX_HIDDEN;
-constexpr int kBfMaxLast = PS_CLOUD_MLP_MAX_LAST;
-constexpr int kBfMaxC0 = PS_CLOUD_MAX_PROP_FEATURES + 3;
-constexpr int64_t kBfMaxBlocks = 1 << 20;
-
-struct BfNet {
-    const uint16_t *W[PS_CLOUD_MLP_MAX_LAYERS];
-    const float *b[PS_CLOUD_MLP_MAX_LAYERS];
-    int c_out[PS_CLOUD_MLP_MAX_LAYERS];
-    int relu[PS_CLOUD_MLP_MAX_LAYERS];
-    int n_layers;
-    int c0;
-};
-
-// Where the rows come from: `rows` [B, R, c0], or (GATHER) the rows of
-// ps_cloud_group: feats[gidx] then xyz[gidx] - xyz[centre_idx], R = s * k.
-struct BfRows {
-    const float *rows;
-    const float *xyz, *feats;
-    const int32_t *centre_idx, *gidx;
-    int n, d, s, k;
-    int R;
-};
 
 // two f32 -> two bf16 (round to nearest even) in one dword, a in the low half
 PS_D uint32_t pack_bf16(float a, float b) {
@@ -102,13 +76,10 @@ PS_D void mma_chunk(f32x16 (&acc)[2], const uint16_t *xin, int pitch, int kcp, c
     }
 }
 
-// the row of the MFMA's result that register r of lane half h holds
-PS_D int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 // x clouds' units, grid stride.  Dynamic LDS: buf0 [64][pitch0] bf16, buf1
 // [64][pitch1] bf16, the running maximum [pool_n] f32.
 template <bool GATHER>
-__global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(BfNet M, BfRows S, int G, float *out,
+__global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(MlpNet<uint16_t> M, MlpRows S, int G, float *out,
                                                                         int64_t out_stride, int out_offset,
                                                                         int64_t units, int64_t units_per_cloud,
                                                                         int pitch0, int pitch1) {
@@ -120,80 +91,54 @@ __global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(BfNet M, 
     uint16_t *buf0 = (uint16_t *)lds_bf, *buf1 = buf0 + kBfRows * pitch0;
     float *pool = (float *)(buf1 + kBfRows * pitch1);
     const int R = S.R, groups = R / G;
-    const int c0 = M.c0, nkc = (c0 + kBfKChunk - 1) / kBfKChunk;
-    const int tiles = G > kBfRows ? (G + kBfRows - 1) / kBfRows : 1;
+    const int c0 = M.c0, nkc = (c0 + kMlpKChunk - 1) / kMlpKChunk;
+    const int tiles = mlp_tiles<kBfRows>(G);
 
     for (int64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
-        const int64_t env = unit / units_per_cloud;
-        const int u = (int)(unit - env * units_per_cloud);
-        // the unit's groups g0 .. g0 + ngroups - 1 of its cloud
-        int g0, ngroups;
-        if (G > kBfRows) {
-            g0 = u;
-            ngroups = 1;
-        } else {
-            const int per = kBfRows / G;
-            g0 = u * per;
-            ngroups = groups - g0 < per ? groups - g0 : per;
-        }
+        const MlpTile U = mlp_unit<kBfRows>(unit, units_per_cloud, G, groups);
         for (int tt = 0; tt < tiles; tt++) {
-            const int r0 = g0 * G + tt * kBfRows;  // the tile's first row of its cloud
-            const int nrows = G > kBfRows ? (G - tt * kBfRows < kBfRows ? G - tt * kBfRows : kBfRows) : ngroups * G;
-            if (GATHER && tid < kBfRows) {
-                int gi = 0;
-                float cx = 0.0f, cy = 0.0f, cz = 0.0f;
-                if (tid < nrows) {
-                    const int r = r0 + tid;
-                    gi = clamp_index(S.gidx[env * R + r], S.n);
-                    const int ci = clamp_index(S.centre_idx[env * S.s + r / S.k], S.n);
-                    const float *c = S.xyz + (env * S.n + ci) * 3;
-                    cx = c[0], cy = c[1], cz = c[2];
-                }
-                s_gi[tid] = gi;
-                s_centre[tid * 3 + 0] = cx;
-                s_centre[tid * 3 + 1] = cy;
-                s_centre[tid * 3 + 2] = cz;
-            }
+            const MlpTile T = mlp_tile<kBfRows>(U, tt, G);
+            if (GATHER) mlp_gather_prologue<kBfRows>(S, T, s_gi, s_centre);
             int c_in = c0;
             for (int l = 0; l < M.n_layers; l++) {
-                const uint16_t *W = nullptr;
-                const float *bias = nullptr;
-                int c_out = 0, relu = 0;
+                // layer l out of the kernel's arguments (no indexed read of them)
+                struct { const uint16_t *W; const float *bias; int c_out, relu; } L = {nullptr, nullptr, 0, 0};
 #pragma unroll
                 for (int q = 0; q < PS_CLOUD_MLP_MAX_LAYERS; q++)
                     if (q == l) {
-                        W = M.W[q];
-                        bias = M.b[q];
-                        c_out = M.c_out[q];
-                        relu = M.relu[q];
+                        L.W = M.W[q];
+                        L.bias = M.b[q];
+                        L.c_out = M.c_out[q];
+                        L.relu = M.relu[q];
                     }
+                const int c_out = L.c_out;
                 const bool last = l == M.n_layers - 1;
                 const int ldw = (c_in + 7) & ~7;
                 // layer l reads buf0 if l is even, buf1 if odd, and writes the other
                 const uint16_t *xin = (l & 1) ? buf1 : buf0;
                 uint16_t *xout = (l & 1) ? buf0 : buf1;
                 const int pin = (l & 1) ? pitch1 : pitch0, pout = (l & 1) ? pitch0 : pitch1;
-                const int nch = (c_out + kBfChunk - 1) / kBfChunk, npass = (nch + nw - 1) / nw;
+                const int nch = (c_out + kMlpChunk - 1) / kMlpChunk, npass = (nch + nw - 1) / nw;
                 for (int pass = 0; pass < npass; pass++) {
-                    const int oc = pass * nw + wave, o0 = oc * kBfChunk;
+                    const int oc = pass * nw + wave, o0 = oc * kMlpChunk;
                     const bool active = oc < nch;
                     const int ch = o0 + j;
                     f32x16 acc[2];
                     if (last) {
-                        const float b0 = (active && ch < c_out) ? bias[ch] : 0.0f;
+                        const float b0 = (active && ch < c_out) ? L.bias[ch] : 0.0f;
 #pragma unroll
                         for (int r = 0; r < 16; r++) acc[0][r] = acc[1][r] = b0;
                     } else {
 #pragma unroll
                         for (int r = 0; r < 16; r++) {
                             const int o = o0 + acc_row(r, h);
-                            acc[0][r] = acc[1][r] = (active && o < c_out) ? bias[o] : 0.0f;
+                            acc[0][r] = acc[1][r] = (active && o < c_out) ? L.bias[o] : 0.0f;
                         }
                     }
                     if (l == 0) {
                         for (int kc = 0; kc < nkc; kc++) {
-                            const int k0 = kc * kBfKChunk;
-                            const int kw = c0 - k0 < kBfKChunk ? c0 - k0 : kBfKChunk;
+                            const int k0 = kc * kMlpKChunk;
+                            const int kw = c0 - k0 < kMlpKChunk ? c0 - k0 : kMlpKChunk;
                             const int kcp = (kw + kBfKStep - 1) & ~(kBfKStep - 1);
                             if (nkc > 1 || pass == 0) {
                                 __syncthreads();  // the rows' indices are written, buf0 is read no more
@@ -203,15 +148,15 @@ __global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(BfNet M, 
                                 lg = lg > 6 ? 6 : lg;
                                 const int lpr = 1 << lg;
                                 for (int i = tid >> lg; i < kBfRows; i += nthreads >> lg) {
-                                    const bool row_in = i < nrows;
+                                    const bool row_in = i < T.nrows;
                                     const float *src = nullptr, *pxyz = nullptr;
                                     if (row_in) {
                                         if (GATHER) {
-                                            const int64_t p = env * S.n + s_gi[i];
+                                            const int64_t p = T.env * S.n + s_gi[i];
                                             src = S.feats + p * S.d;
                                             pxyz = S.xyz + p * 3;
                                         } else {
-                                            src = S.rows + (env * R + r0 + i) * c0;
+                                            src = S.rows + (T.env * R + T.r0 + i) * c0;
                                         }
                                     }
                                     for (int c = tid & (lpr - 1); c < kcp2; c += lpr) {
@@ -234,26 +179,20 @@ __global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(BfNet M, 
                             }
                             if (active) {
                                 if (last)
-                                    mma_chunk<false>(acc, buf0, pitch0, kcp, W, ldw, c_out, o0, k0);
+                                    mma_chunk<false>(acc, buf0, pitch0, kcp, L.W, ldw, c_out, o0, k0);
                                 else
-                                    mma_chunk<true>(acc, buf0, pitch0, kcp, W, ldw, c_out, o0, k0);
+                                    mma_chunk<true>(acc, buf0, pitch0, kcp, L.W, ldw, c_out, o0, k0);
                             }
                         }
                     } else if (active) {
                         const int kcp = (c_in + kBfKStep - 1) & ~(kBfKStep - 1);
                         if (last)
-                            mma_chunk<false>(acc, xin, pin, kcp, W, ldw, c_out, o0, 0);
+                            mma_chunk<false>(acc, xin, pin, kcp, L.W, ldw, c_out, o0, 0);
                         else
-                            mma_chunk<true>(acc, xin, pin, kcp, W, ldw, c_out, o0, 0);
+                            mma_chunk<true>(acc, xin, pin, kcp, L.W, ldw, c_out, o0, 0);
                     }
                     if (!active) continue;
-                    if (relu) {
-#pragma unroll
-                        for (int r = 0; r < 16; r++) {
-                            acc[0][r] = acc[0][r] > 0.0f ? acc[0][r] : 0.0f;
-                            acc[1][r] = acc[1][r] > 0.0f ? acc[1][r] : 0.0f;
-                        }
-                    }
+                    mlp_relu(acc, L.relu);
                     if (!last) {
                         // lane j holds tile rows j and 32 + j; registers 4 g .. 4 g + 3 are the channels
                         // o0 + 8 g + 4 h + 0 .. 3.  Channels past c_out of the chunk are exact zeros
@@ -271,19 +210,19 @@ __global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(BfNet M, 
                         }
                     } else if (G == 1) {
                         if (ch < c_out) {
-                            float *o = out + (env * R + r0) * out_stride + out_offset + ch;
+                            float *o = out + (T.env * R + T.r0) * out_stride + out_offset + ch;
 #pragma unroll
                             for (int m = 0; m < 2; m++)
 #pragma unroll
                                 for (int r = 0; r < 16; r++) {
                                     const int row = 32 * m + acc_row(r, h);
-                                    if (row < nrows) o[(int64_t)row * out_stride] = acc[m][r];
+                                    if (row < T.nrows) o[(int64_t)row * out_stride] = acc[m][r];
                                 }
                         }
                     } else {
                         // G > 64: the one group's rows of this tile; else each whole group of the tile
-                        const int span = G > kBfRows ? nrows : G;
-                        for (int g = 0; g < ngroups; g++) {
+                        const int span = G > kBfRows ? T.nrows : G;
+                        for (int g = 0; g < T.ngroups; g++) {
                             const int lo = g * span, hi = lo + span;
                             float mx = -INFINITY;
 #pragma unroll
@@ -297,7 +236,7 @@ __global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(BfNet M, 
                             if (h == 0 && ch < c_out) {
                                 if (tt > 0) mx = fmaxf(mx, pool[ch]);  // written by this lane, a tile ago
                                 if (tt == tiles - 1)
-                                    out[(env * groups + g0 + g) * out_stride + out_offset + ch] = mx;
+                                    out[(T.env * groups + T.g0 + g) * out_stride + out_offset + ch] = mx;
                                 else
                                     pool[ch] = mx;
                             }
@@ -312,61 +251,20 @@ __global__ __launch_bounds__(kBfMaxWaves * 64) void k_cloud_mlp_bfloat(BfNet M, 
 }
 
 // ------------------------------------------------------------- host side
-inline int pitch_of(int width) { return ((width + kBfChunk - 1) / kBfChunk) * kBfChunk + kBfPad; }
+inline int pitch_of(int width) { return ((width + kMlpChunk - 1) / kMlpChunk) * kMlpChunk + kBfPad; }
 
 constexpr size_t kBfMaxLds =
-    sizeof(uint16_t) * kBfRows * 2 * (kBfMaxHidden + kBfPad) + sizeof(float) * kBfMaxLast;
-
-inline const char *net_error(const ps_cloud_mlp_bfloat_layer *layers, int n_layers, int c0, int64_t out_stride,
-                             int out_offset) {
-    if (n_layers < 1 || n_layers > PS_CLOUD_MLP_MAX_LAYERS) return "n_layers outside 1..4";
-    if (c0 < 1 || c0 > kBfMaxC0) return "C0 outside 1..2051";
-    for (int l = 0; l < n_layers; l++) {
-        if (!layers[l].W || !layers[l].b) return "a layer without W or b";
-        if (((uintptr_t)layers[l].W & 15) != 0) return "a layer's W is not 16-byte aligned";
-        const int most = l == n_layers - 1 ? kBfMaxLast : kBfMaxHidden;
-        if (layers[l].c_out < 1 || layers[l].c_out > most) return "c_out outside 1..512 (the last: 1..1024)";
-    }
-    if (out_offset < 0 || out_stride < (int64_t)out_offset + layers[n_layers - 1].c_out)
-        return "out_offset < 0 or out_stride < out_offset + the last c_out";
-    return nullptr;
-}
+    sizeof(uint16_t) * kBfRows * 2 * (kMlpMaxHidden + kBfPad) + sizeof(float) * kMlpMaxLast;
+static_assert(kBfMaxLds + 2048 <= 160 * 1024, "the largest network must fit the 160 KiB of LDS");
 
 template <bool GATHER>
-int launch_mlp(ps_ctx *c, const ps_cloud_mlp_bfloat_layer *layers, int n_layers, int c0, BfRows S, int G, float *out,
-               int64_t out_stride, int out_offset, hipStream_t st) {
-    BfNet M;
-    memset(&M, 0, sizeof M);
-    M.n_layers = n_layers;
-    M.c0 = c0;
-    int widest = 0, w0 = c0 < kBfKChunk ? c0 : kBfKChunk, w1 = 1;
-    for (int l = 0; l < n_layers; l++) {
-        M.W[l] = layers[l].W;
-        M.b[l] = layers[l].b;
-        M.c_out[l] = layers[l].c_out;
-        M.relu[l] = layers[l].relu != 0;
-        if (layers[l].c_out > widest) widest = layers[l].c_out;
-        if (l < n_layers - 1) {  // layer 0 writes buf1, layer 1 buf0, layer 2 buf1
-            int &w = (l & 1) ? w0 : w1;
-            if (layers[l].c_out > w) w = layers[l].c_out;
-        }
-    }
-    int nw = (widest + kBfChunk - 1) / kBfChunk;
-    nw = nw >= 8 ? 8 : (nw >= 4 ? 4 : (nw >= 2 ? 2 : 1));
-    const int pitch0 = pitch_of(w0), pitch1 = pitch_of(w1);
-    const int pool_n = G > kBfRows ? layers[n_layers - 1].c_out : 0;
-    const size_t lds = sizeof(uint16_t) * (size_t)kBfRows * (pitch0 + pitch1) + sizeof(float) * pool_n;
-    const int groups = S.R / G;
-    const int64_t upc = G > kBfRows ? groups : (groups + kBfRows / G - 1) / (kBfRows / G);
-    const int64_t units = upc * c->num_envs;
-    static_assert(kBfMaxLds + 2048 <= 160 * 1024, "the largest network must fit the 160 KiB of LDS");
-    if (hipFuncSetAttribute((const void *)k_cloud_mlp_bfloat<GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kBfMaxLds) != hipSuccess)
-        return fail(c, PS_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    const int64_t blocks = units < kBfMaxBlocks ? units : kBfMaxBlocks;
-    hipLaunchKernelGGL(k_cloud_mlp_bfloat<GATHER>, dim3((unsigned)blocks), dim3(nw * 64), lds, st, M, S, G, out,
-                       out_stride, out_offset, units, upc, pitch0, pitch1);
-    return check_launch(c);
+int launch_mlp(ps_ctx *c, const ps_cloud_mlp_bfloat_layer *layers, int n_layers, int c0, const MlpRows &S, int G,
+               float *out, int64_t out_stride, int out_offset, void *stream) {
+    MlpNet<uint16_t> M;
+    const MlpPlan P = mlp_plan<kBfRows, kBfMaxWaves>(c, layers, n_layers, c0, S.R, G, pitch_of, M);
+    const size_t lds = sizeof(uint16_t) * (size_t)kBfRows * (P.pitch0 + P.pitch1) + sizeof(float) * P.pool_n;
+    return mlp_launch<uint16_t>(c, k_cloud_mlp_bfloat<GATHER>, P, lds, kBfMaxLds, M, S, G, out, out_stride, out_offset,
+                                (hipStream_t)stream);
 }
 
 }  // namespace
@@ -375,35 +273,19 @@ extern "C" {
 
 int ps_cloud_mlp_bfloat(ps_ctx *c, const float *rows, int R, int C0, const ps_cloud_mlp_bfloat_layer *layers,
                         int n_layers, int G, float *out, int64_t out_stride, int out_offset, void *stream) {
-    if (!c || !rows || !layers || !out) return fail(c, PS_ERR_ARG, "null argument");
-    if (const char *e = net_error(layers, n_layers, C0, out_stride, out_offset)) return fail(c, PS_ERR_ARG, e);
-    if (R < 1 || G < 1 || R % G != 0) return fail(c, PS_ERR_ARG, "R < 1, G < 1 or R not a multiple of G");
-    BfRows S;
-    memset(&S, 0, sizeof S);
-    S.rows = rows;
-    S.R = R;
-    return launch_mlp<false>(c, layers, n_layers, C0, S, G, out, out_stride, out_offset, (hipStream_t)stream);
+    MlpRows S;
+    if (int e = mlp_args(c, rows, R, C0, layers, n_layers, G, out, out_stride, out_offset, S)) return e;
+    return launch_mlp<false>(c, layers, n_layers, C0, S, G, out, out_stride, out_offset, stream);
 }
 
 int ps_cloud_group_mlp_bfloat(ps_ctx *c, const float *xyz, const float *feats, int N, int D, const int32_t *centre_idx,
                               int S, const int32_t *group_idx, int K, const ps_cloud_mlp_bfloat_layer *layers,
                               int n_layers, float *out, int64_t out_stride, int out_offset, void *stream) {
-    if (!c || !xyz || !centre_idx || !group_idx || !layers || !out) return fail(c, PS_ERR_ARG, "null argument");
-    if (N < 1 || N > PS_CLOUD_MAX_POINTS) return fail(c, PS_ERR_ARG, "N outside 1..8192");
-    if (S < 1 || S > N) return fail(c, PS_ERR_ARG, "S outside 1..N");
-    if (K < 1 || (int64_t)S * K > 0x7fffffff) return fail(c, PS_ERR_ARG, "nsample < 1 (or S * nsample >= 2^31)");
-    if (D < 0 || D > PS_CLOUD_MAX_PROP_FEATURES || (feats == nullptr) != (D == 0))
-        return fail(c, PS_ERR_ARG, "D outside 0..2048, or D and feats disagree");
-    if (const char *e = net_error(layers, n_layers, D + 3, out_stride, out_offset)) return fail(c, PS_ERR_ARG, e);
-    BfRows Q;
-    memset(&Q, 0, sizeof Q);
-    Q.xyz = xyz;
-    Q.feats = feats;
-    Q.centre_idx = centre_idx;
-    Q.gidx = group_idx;
-    Q.n = N, Q.d = D, Q.s = S, Q.k = K;
-    Q.R = S * K;
-    return launch_mlp<true>(c, layers, n_layers, D + 3, Q, K, out, out_stride, out_offset, (hipStream_t)stream);
+    MlpRows Q;
+    if (int e = group_mlp_args(c, xyz, feats, N, D, centre_idx, S, group_idx, K, layers, n_layers, out, out_stride,
+                               out_offset, Q))
+        return e;
+    return launch_mlp<true>(c, layers, n_layers, D + 3, Q, K, out, out_stride, out_offset, stream);
 }
 
 }  // extern "C"

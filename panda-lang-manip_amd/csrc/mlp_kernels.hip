@@ -4,19 +4,15 @@
 // over groups of G rows, on the f32-input MFMA (v_mfma_f32_32x32x2_f32).
 //
 // One kernel, k_cloud_mlp<GATHER>: a workgroup of 1, 2 or 4 waves owns a tile
-// of 32 rows.  The tile's activations stay in LDS from the first layer to the
-// last ([row][channel], two buffers the layers alternate between); the waves
-// share the rows and split a layer's output channels in chunks of 32, so an
-// MFMA's 32 x 32 result is 32 rows (in its registers) by 32 channels (on its
-// lanes).  A wave stages its chunk's weights W[32 outputs][32 k] through a
-// slab of LDS of its own: coalesced along k from global memory, the next slab
-// in flight while the current one is multiplied.  Rows come from memory
-// directly or, with GATHER, through group_idx as ps_cloud_group composes them,
-// so the grouped tensor never exists.  A first layer wider than kMlpKChunk is
-// streamed through LDS in chunks of k with the accumulators kept.  The last
-// layer's result goes from the accumulators to `out` (G = 1) or into the
-// maximum of its group; a group longer than a tile is walked tile by tile by
-// one workgroup with the running maximum in LDS.
+// of 32 rows.  The tile, its rows' sources, the layers' buffers and the host
+// side are ps_mlp_tile.h's, shared with the bfloat16 kernel; this file has the
+// f32 multiplication and the kernel body (the layer select and
+// the last layer's epilogue measured slower as shared functions).  An MFMA's
+// 32 x 32 result is 32 rows (in its registers) by 32 channels (on its lanes).
+// A wave stages its chunk's weights W[32 outputs][32 k] through a slab of LDS
+// of its own: coalesced along k from global memory, the next slab in flight
+// while the current one is multiplied.  A first layer wider than kMlpKChunk is
+// streamed through LDS in chunks of k with the accumulators kept.
 //
 // The arithmetic (include/pandasim.h): an accumulator starts as the bias and
 // takes k in ascending order, one MFMA per two k; k is padded to a multiple of
@@ -26,41 +22,14 @@
 // 4 * (c & 1) + (c >> 1), so that the lanes of half h = lane >> 5 (which hold
 // k = 2 s + h of MFMA s) read their four operands of four MFMAs as one 128-bit
 // word at 4 h.
-#include "ps_cloud_math.h"
+#include "ps_mlp_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kMlpRows = 32;      // rows of a tile: the MFMA's M
-constexpr int kMlpChunk = 32;     // output channels of one accumulator: the MFMA's N
 constexpr int kMlpMaxWaves = 4;
-constexpr int kMlpKChunk = 512;   // most input channels resident in LDS (= the hidden limit)
 constexpr int kMlpSlab = 32;      // k of one weight slab
 constexpr int kMlpSlabPitch = 36; // floats per slab row: 16-byte aligned, 4 banks past a multiple of 32
-constexpr int kMlpMaxHidden = PS_CLOUD_MLP_MAX_HIDDEN;
-constexpr int kMlpMaxLast = PS_CLOUD_MLP_MAX_LAST;
-constexpr int kMlpMaxC0 = PS_CLOUD_MAX_PROP_FEATURES + 3;
-constexpr int64_t kMlpMaxBlocks = 1 << 20;
-
-struct MlpNet {
-    const float *W[PS_CLOUD_MLP_MAX_LAYERS];
-    const float *b[PS_CLOUD_MLP_MAX_LAYERS];
-    int c_out[PS_CLOUD_MLP_MAX_LAYERS];
-    int relu[PS_CLOUD_MLP_MAX_LAYERS];
-    int n_layers;
-    int c0;
-};
-
-// Where the rows come from: `rows` [B, R, c0], or (GATHER) the rows of
-// ps_cloud_group: feats[gidx] then xyz[gidx] - xyz[centre_idx], R = s * k.
-struct MlpRows {
-    const float *rows;
-    const float *xyz, *feats;
-    const int32_t *centre_idx, *gidx;
-    int n, d, s, k;
-    int R;
-};
 
 PS_D int k_slot(int c) { return (c & ~7) | ((c & 1) << 2) | ((c >> 1) & 3); }
 
@@ -113,13 +82,10 @@ PS_D void mma_chunk(f32x16 &acc, const float *xin, int pitch, int kcp, const flo
     }
 }
 
-// the tile row that register r of lane half h holds
-PS_D int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
 // x clouds' units, grid stride.  Dynamic LDS: buf0 [32][pitch0], buf1
 // [32][pitch1], a slab per wave, the running maximum [pool_n].
 template <bool GATHER>
-__global__ __launch_bounds__(kMlpMaxWaves * 64) void k_cloud_mlp(MlpNet M, MlpRows S, int G, float *out,
+__global__ __launch_bounds__(kMlpMaxWaves * 64) void k_cloud_mlp(MlpNet<float> M, MlpRows S, int G, float *out,
                                                                   int64_t out_stride, int out_offset, int64_t units,
                                                                   int64_t units_per_cloud, int pitch0, int pitch1) {
 #pragma clang fp contract(off)
@@ -133,51 +99,26 @@ __global__ __launch_bounds__(kMlpMaxWaves * 64) void k_cloud_mlp(MlpNet M, MlpRo
     float *pool = buf1 + kMlpRows * pitch1 + nw * (kMlpRows * kMlpSlabPitch);
     const int R = S.R, groups = R / G;
     const int c0 = M.c0, nkc = (c0 + kMlpKChunk - 1) / kMlpKChunk;
-    const int tiles = G > kMlpRows ? (G + kMlpRows - 1) / kMlpRows : 1;
+    const int tiles = mlp_tiles<kMlpRows>(G);
 
     for (int64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
-        const int64_t env = unit / units_per_cloud;
-        const int u = (int)(unit - env * units_per_cloud);
-        // the unit's groups g0 .. g0 + ngroups - 1 of its cloud
-        int g0, ngroups;
-        if (G > kMlpRows) {
-            g0 = u;
-            ngroups = 1;
-        } else {
-            const int per = kMlpRows / G;
-            g0 = u * per;
-            ngroups = groups - g0 < per ? groups - g0 : per;
-        }
+        const MlpTile U = mlp_unit<kMlpRows>(unit, units_per_cloud, G, groups);
         for (int tt = 0; tt < tiles; tt++) {
-            const int r0 = g0 * G + tt * kMlpRows;  // the tile's first row of its cloud
-            const int nrows = G > kMlpRows ? (G - tt * kMlpRows < kMlpRows ? G - tt * kMlpRows : kMlpRows) : ngroups * G;
-            if (GATHER && tid < kMlpRows) {
-                int gi = 0;
-                float cx = 0.0f, cy = 0.0f, cz = 0.0f;
-                if (tid < nrows) {
-                    const int r = r0 + tid;
-                    gi = clamp_index(S.gidx[env * R + r], S.n);
-                    const int ci = clamp_index(S.centre_idx[env * S.s + r / S.k], S.n);
-                    const float *c = S.xyz + (env * S.n + ci) * 3;
-                    cx = c[0], cy = c[1], cz = c[2];
-                }
-                s_gi[tid] = gi;
-                s_centre[tid * 3 + 0] = cx;
-                s_centre[tid * 3 + 1] = cy;
-                s_centre[tid * 3 + 2] = cz;
-            }
+            const MlpTile T = mlp_tile<kMlpRows>(U, tt, G);
+            if (GATHER) mlp_gather_prologue<kMlpRows>(S, T, s_gi, s_centre);
             int c_in = c0;
             for (int l = 0; l < M.n_layers; l++) {
-                const float *W = nullptr, *bias = nullptr;
-                int c_out = 0, relu = 0;
+                // layer l out of the kernel's arguments (no indexed read of them)
+                struct { const float *W; const float *bias; int c_out, relu; } L = {nullptr, nullptr, 0, 0};
 #pragma unroll
                 for (int q = 0; q < PS_CLOUD_MLP_MAX_LAYERS; q++)
                     if (q == l) {
-                        W = M.W[q];
-                        bias = M.b[q];
-                        c_out = M.c_out[q];
-                        relu = M.relu[q];
+                        L.W = M.W[q];
+                        L.bias = M.b[q];
+                        L.c_out = M.c_out[q];
+                        L.relu = M.relu[q];
                     }
+                const int c_out = L.c_out;
                 const bool last = l == M.n_layers - 1;
                 // layer l reads buf0 if l is even, buf1 if odd, and writes the other
                 const float *xin = (l & 1) ? buf1 : buf0;
@@ -188,10 +129,10 @@ __global__ __launch_bounds__(kMlpMaxWaves * 64) void k_cloud_mlp(MlpNet M, MlpRo
                     const int oc = pass * nw + wave, o0 = oc * kMlpChunk;
                     const bool active = oc < nch;
                     const int ch = o0 + j;
-                    const float b0 = (active && ch < c_out) ? bias[ch] : 0.0f;
-                    f32x16 acc;
+                    const float b0 = (active && ch < c_out) ? L.bias[ch] : 0.0f;
+                    f32x16 acc[1];
 #pragma unroll
-                    for (int r = 0; r < 16; r++) acc[r] = b0;
+                    for (int r = 0; r < 16; r++) acc[0][r] = b0;
                     if (l == 0) {
                         for (int kc = 0; kc < nkc; kc++) {
                             const int k0 = kc * kMlpKChunk;
@@ -201,59 +142,58 @@ __global__ __launch_bounds__(kMlpMaxWaves * 64) void k_cloud_mlp(MlpNet M, MlpRo
                                 for (int e = tid; e < kMlpRows * kcp; e += nthreads) {
                                     const int i = e / kcp, kk = e - i * kcp, k = k0 + kk;
                                     float v = 0.0f;
-                                    if (i < nrows && kk < kw) {
+                                    if (i < T.nrows && kk < kw) {
                                         if (GATHER) {
-                                            const int64_t p = env * S.n + s_gi[i];
+                                            const int64_t p = T.env * S.n + s_gi[i];
                                             v = k < S.d ? S.feats[p * S.d + k]
                                                         : S.xyz[p * 3 + (k - S.d)] - s_centre[i * 3 + (k - S.d)];
                                         } else {
-                                            v = S.rows[(env * R + r0 + i) * c0 + k];
+                                            v = S.rows[(T.env * R + T.r0 + i) * c0 + k];
                                         }
                                     }
                                     buf0[i * pitch0 + k_slot(kk)] = v;
                                 }
                                 __syncthreads();
                             }
-                            if (active) mma_chunk(acc, buf0, pitch0, kcp, W, c_in, c_out, o0, k0, wst);
+                            if (active) mma_chunk(acc[0], buf0, pitch0, kcp, L.W, c_in, c_out, o0, k0, wst);
                         }
                     } else if (active) {
-                        mma_chunk(acc, xin, pin, (c_in + 7) & ~7, W, c_in, c_out, o0, 0, wst);
+                        mma_chunk(acc[0], xin, pin, (c_in + 7) & ~7, L.W, c_in, c_out, o0, 0, wst);
                     }
                     if (!active) continue;
-                    if (relu) {
-#pragma unroll
-                        for (int r = 0; r < 16; r++) acc[r] = acc[r] > 0.0f ? acc[r] : 0.0f;
-                    }
+                    mlp_relu(acc, L.relu);
                     if (!last) {
                         // channels past c_out of the chunk are exact zeros (zero weights and bias)
                         float *o = xout + o0 + k_slot(j);
 #pragma unroll
-                        for (int r = 0; r < 16; r++) o[acc_row(r, h) * pout] = acc[r];
+                        for (int r = 0; r < 16; r++) o[acc_row(r, h) * pout] = acc[0][r];
                     } else if (G == 1) {
                         if (ch < c_out) {
-                            float *o = out + (env * R + r0) * out_stride + out_offset + ch;
-#pragma unroll
-                            for (int r = 0; r < 16; r++)
-                                if (acc_row(r, h) < nrows) o[(int64_t)acc_row(r, h) * out_stride] = acc[r];
-                        }
-                    } else {
-                        // G > 32: the one group's rows of this tile; else each whole group of the tile
-                        const int span = G > kMlpRows ? nrows : G;
-                        for (int g = 0; g < ngroups; g++) {
-                            const int lo = g * span, hi = lo + span;
-                            float m = -INFINITY;
+                            float *o = out + (T.env * R + T.r0) * out_stride + out_offset + ch;
 #pragma unroll
                             for (int r = 0; r < 16; r++) {
                                 const int row = acc_row(r, h);
-                                m = (row >= lo && row < hi) ? fmaxf(m, acc[r]) : m;
+                                if (row < T.nrows) o[(int64_t)row * out_stride] = acc[0][r];
                             }
-                            m = fmaxf(m, __shfl_xor(m, 32));
+                        }
+                    } else {
+                        // G > 32: the one group's rows of this tile; else each whole group of the tile
+                        const int span = G > kMlpRows ? T.nrows : G;
+                        for (int g = 0; g < T.ngroups; g++) {
+                            const int lo = g * span, hi = lo + span;
+                            float mx = -INFINITY;
+#pragma unroll
+                            for (int r = 0; r < 16; r++) {
+                                const int row = acc_row(r, h);
+                                mx = (row >= lo && row < hi) ? fmaxf(mx, acc[0][r]) : mx;
+                            }
+                            mx = fmaxf(mx, __shfl_xor(mx, 32));
                             if (h == 0 && ch < c_out) {
-                                if (tt > 0) m = fmaxf(m, pool[ch]);  // written by this lane, a tile ago
+                                if (tt > 0) mx = fmaxf(mx, pool[ch]);  // written by this lane, a tile ago
                                 if (tt == tiles - 1)
-                                    out[(env * groups + g0 + g) * out_stride + out_offset + ch] = m;
+                                    out[(T.env * groups + T.g0 + g) * out_stride + out_offset + ch] = mx;
                                 else
-                                    pool[ch] = m;
+                                    pool[ch] = mx;
                             }
                         }
                     }
@@ -268,58 +208,19 @@ __global__ __launch_bounds__(kMlpMaxWaves * 64) void k_cloud_mlp(MlpNet M, MlpRo
 // ------------------------------------------------------------- host side
 inline int pitch_of(int width) { return ((width + kMlpChunk - 1) / kMlpChunk) * kMlpChunk + 4; }
 
-inline const char *net_error(const ps_cloud_mlp_layer *layers, int n_layers, int c0, int64_t out_stride,
-                             int out_offset) {
-    if (n_layers < 1 || n_layers > PS_CLOUD_MLP_MAX_LAYERS) return "n_layers outside 1..4";
-    if (c0 < 1 || c0 > kMlpMaxC0) return "C0 outside 1..2051";
-    for (int l = 0; l < n_layers; l++) {
-        if (!layers[l].W || !layers[l].b) return "a layer without W or b";
-        const int most = l == n_layers - 1 ? kMlpMaxLast : kMlpMaxHidden;
-        if (layers[l].c_out < 1 || layers[l].c_out > most) return "c_out outside 1..512 (the last: 1..1024)";
-    }
-    if (out_offset < 0 || out_stride < (int64_t)out_offset + layers[n_layers - 1].c_out)
-        return "out_offset < 0 or out_stride < out_offset + the last c_out";
-    return nullptr;
-}
+constexpr size_t kMlpMaxLds =
+    sizeof(float) * (kMlpRows * 2 * (kMlpMaxHidden + 4) + kMlpMaxWaves * kMlpRows * kMlpSlabPitch + kMlpMaxLast);
+static_assert(kMlpMaxLds + 1024 <= 160 * 1024, "the largest network must fit the 160 KiB of LDS");
 
 template <bool GATHER>
-int launch_mlp(ps_ctx *c, const ps_cloud_mlp_layer *layers, int n_layers, int c0, MlpRows S, int G, float *out,
-               int64_t out_stride, int out_offset, hipStream_t st) {
-    MlpNet M;
-    memset(&M, 0, sizeof M);
-    M.n_layers = n_layers;
-    M.c0 = c0;
-    int widest = 0, w0 = c0 < kMlpKChunk ? c0 : kMlpKChunk, w1 = 1;
-    for (int l = 0; l < n_layers; l++) {
-        M.W[l] = layers[l].W;
-        M.b[l] = layers[l].b;
-        M.c_out[l] = layers[l].c_out;
-        M.relu[l] = layers[l].relu != 0;
-        if (layers[l].c_out > widest) widest = layers[l].c_out;
-        if (l < n_layers - 1) {  // layer 0 writes buf1, layer 1 buf0, layer 2 buf1
-            int &w = (l & 1) ? w0 : w1;
-            if (layers[l].c_out > w) w = layers[l].c_out;
-        }
-    }
-    int nw = (widest + kMlpChunk - 1) / kMlpChunk;
-    nw = nw >= 4 ? 4 : (nw >= 2 ? 2 : 1);
-    const int pitch0 = pitch_of(w0), pitch1 = pitch_of(w1);
-    const int pool_n = G > kMlpRows ? layers[n_layers - 1].c_out : 0;
-    const size_t lds = sizeof(float) * ((size_t)kMlpRows * (pitch0 + pitch1) + (size_t)nw * kMlpRows * kMlpSlabPitch +
-                                        pool_n);
-    const int groups = S.R / G;
-    const int64_t upc = G > kMlpRows ? groups : (groups + kMlpRows / G - 1) / (kMlpRows / G);
-    const int64_t units = upc * c->num_envs;
-    static_assert(sizeof(float) * (kMlpRows * 2 * (kMlpMaxHidden + 4) + kMlpMaxWaves * kMlpRows * kMlpSlabPitch +
-                                   kMlpMaxLast) + 1024 <= 160 * 1024, "the largest network must fit the 160 KiB of LDS");
-    if (hipFuncSetAttribute((const void *)k_cloud_mlp<GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(sizeof(float) * (kMlpRows * 2 * (kMlpMaxHidden + 4) +
-                                                   kMlpMaxWaves * kMlpRows * kMlpSlabPitch + kMlpMaxLast))) != hipSuccess)
-        return fail(c, PS_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    const int64_t blocks = units < kMlpMaxBlocks ? units : kMlpMaxBlocks;
-    hipLaunchKernelGGL(k_cloud_mlp<GATHER>, dim3((unsigned)blocks), dim3(nw * 64), lds, st, M, S, G, out, out_stride,
-                       out_offset, units, upc, pitch0, pitch1);
-    return check_launch(c);
+int launch_mlp(ps_ctx *c, const ps_cloud_mlp_layer *layers, int n_layers, int c0, const MlpRows &S, int G, float *out,
+               int64_t out_stride, int out_offset, void *stream) {
+    MlpNet<float> M;
+    const MlpPlan P = mlp_plan<kMlpRows, kMlpMaxWaves>(c, layers, n_layers, c0, S.R, G, pitch_of, M);
+    const size_t lds = sizeof(float) * ((size_t)kMlpRows * (P.pitch0 + P.pitch1) +
+                                        (size_t)P.nw * kMlpRows * kMlpSlabPitch + P.pool_n);
+    return mlp_launch<float>(c, k_cloud_mlp<GATHER>, P, lds, kMlpMaxLds, M, S, G, out, out_stride, out_offset,
+                             (hipStream_t)stream);
 }
 
 }  // namespace
@@ -328,35 +229,19 @@ extern "C" {
 
 int ps_cloud_mlp(ps_ctx *c, const float *rows, int R, int C0, const ps_cloud_mlp_layer *layers, int n_layers, int G,
                  float *out, int64_t out_stride, int out_offset, void *stream) {
-    if (!c || !rows || !layers || !out) return fail(c, PS_ERR_ARG, "null argument");
-    if (const char *e = net_error(layers, n_layers, C0, out_stride, out_offset)) return fail(c, PS_ERR_ARG, e);
-    if (R < 1 || G < 1 || R % G != 0) return fail(c, PS_ERR_ARG, "R < 1, G < 1 or R not a multiple of G");
     MlpRows S;
-    memset(&S, 0, sizeof S);
-    S.rows = rows;
-    S.R = R;
-    return launch_mlp<false>(c, layers, n_layers, C0, S, G, out, out_stride, out_offset, (hipStream_t)stream);
+    if (int e = mlp_args(c, rows, R, C0, layers, n_layers, G, out, out_stride, out_offset, S)) return e;
+    return launch_mlp<false>(c, layers, n_layers, C0, S, G, out, out_stride, out_offset, stream);
 }
 
 int ps_cloud_group_mlp(ps_ctx *c, const float *xyz, const float *feats, int N, int D, const int32_t *centre_idx, int S,
                        const int32_t *group_idx, int K, const ps_cloud_mlp_layer *layers, int n_layers, float *out,
                        int64_t out_stride, int out_offset, void *stream) {
-    if (!c || !xyz || !centre_idx || !group_idx || !layers || !out) return fail(c, PS_ERR_ARG, "null argument");
-    if (N < 1 || N > PS_CLOUD_MAX_POINTS) return fail(c, PS_ERR_ARG, "N outside 1..8192");
-    if (S < 1 || S > N) return fail(c, PS_ERR_ARG, "S outside 1..N");
-    if (K < 1 || (int64_t)S * K > 0x7fffffff) return fail(c, PS_ERR_ARG, "nsample < 1 (or S * nsample >= 2^31)");
-    if (D < 0 || D > PS_CLOUD_MAX_PROP_FEATURES || (feats == nullptr) != (D == 0))
-        return fail(c, PS_ERR_ARG, "D outside 0..2048, or D and feats disagree");
-    if (const char *e = net_error(layers, n_layers, D + 3, out_stride, out_offset)) return fail(c, PS_ERR_ARG, e);
     MlpRows Q;
-    memset(&Q, 0, sizeof Q);
-    Q.xyz = xyz;
-    Q.feats = feats;
-    Q.centre_idx = centre_idx;
-    Q.gidx = group_idx;
-    Q.n = N, Q.d = D, Q.s = S, Q.k = K;
-    Q.R = S * K;
-    return launch_mlp<true>(c, layers, n_layers, D + 3, Q, K, out, out_stride, out_offset, (hipStream_t)stream);
+    if (int e = group_mlp_args(c, xyz, feats, N, D, centre_idx, S, group_idx, K, layers, n_layers, out, out_stride,
+                               out_offset, Q))
+        return e;
+    return launch_mlp<true>(c, layers, n_layers, D + 3, Q, K, out, out_stride, out_offset, stream);
 }
 
 }  // extern "C"

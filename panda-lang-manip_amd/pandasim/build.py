@@ -98,7 +98,8 @@ VARIANTS = {"": [], "prof": ["-DPS_PROFILE_PHASES"]}
 
 
 def headers() -> list:
-    """Every header the objects include: csrc/*.h and include/*.h."""
+    """Every header the objects include: csrc/*.h (ps_mlp_tile.h, which the
+    two shared-MLP units share, among them) and include/*.h."""
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hs += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h")]
     return sorted(hs)

@@ -18,46 +18,30 @@ import torch
 
 from bfloat_reference import (dyadic_net, dyadic_rows, exact_in_f32, mlp_bfloat_np, mlp_bfloat_with_bound,
                               segnet_bfloat_np)
-from cloud_helpers import DEV, dev, make_sims, raw_call, raw_group, same_bits
+import cloud_helpers
+from cloud_helpers import DEV, SENTINEL, dev, make_sims, net, random_groups, raw_call, raw_group, same_bits
 from cloud_reference import group_rows_np
-from test_gpu_mlp import SENTINEL, net, random_groups
 from test_mlp_cpu import CASES, case_of, folded, golden
 
 pytestmark = pytest.mark.gpu
 
 
+# the shared helpers at this module's precision and entry points
+def upload(layers, precision="bfloat16"):
+    return cloud_helpers.upload(layers, precision)
+
+
+def raw_mlp(*args, **kwargs):
+    return cloud_helpers.raw_mlp(*args, suffix="_bfloat", **kwargs)
+
+
+def raw_group_mlp(*args, **kwargs):
+    return cloud_helpers.raw_group_mlp(*args, suffix="_bfloat", **kwargs)
+
+
 @pytest.fixture(scope="module")
 def sims():
     return make_sims((2, 1, 7))
-
-
-def upload(layers, precision="bfloat16"):
-    from pandasim import CloudMlp
-
-    return CloudMlp(layers, DEV, precision=precision)
-
-
-def raw_mlp(sim, rows, mlp, pool=1, out=None, offset=0, expect=0):
-    from pandasim.sim import _ptr
-
-    nb, r, c0 = rows.shape
-    if out is None:
-        out = torch.full((nb, r // pool, mlp.widths[-1]), SENTINEL, device=DEV)
-    assert raw_call(sim, "ps_cloud_mlp_bfloat", sim._ctx, _ptr(rows), r, c0, mlp.array, len(mlp), pool, _ptr(out),
-                    out.shape[2], offset, sim._stream()) == expect
-    return out
-
-
-def raw_group_mlp(sim, xyz, feats, centre_idx, gidx, mlp, out=None, offset=0, expect=0):
-    from pandasim.sim import _ptr
-
-    nb, n = xyz.shape[:2]
-    d, (s, k) = 0 if feats is None else feats.shape[2], gidx.shape[1:]
-    if out is None:
-        out = torch.full((nb, s, mlp.widths[-1]), SENTINEL, device=DEV)
-    assert raw_call(sim, "ps_cloud_group_mlp_bfloat", sim._ctx, _ptr(xyz), _ptr(feats), n, d, _ptr(centre_idx), s,
-                    _ptr(gidx), k, mlp.array, len(mlp), _ptr(out), out.shape[2], offset, sim._stream()) == expect
-    return out
 
 
 def equals(got, want):

@@ -12,13 +12,12 @@ import numpy as np
 import pytest
 import torch
 
-from cloud_helpers import DEV, dev, make_sims, raw_call, raw_group
+from cloud_helpers import (DEV, SENTINEL, dev, make_sims, net, random_groups, raw_call, raw_group, raw_group_mlp, raw_mlp,
+                           upload)
 from cloud_reference import group_rows_np, mlp_np
 from test_mlp_cpu import CASES, case_of, folded, golden, restated
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -12345.5
 
 
 @pytest.fixture(scope="module")
@@ -30,64 +29,6 @@ def sims():
 def same_values(got, want):
     got = got.cpu().numpy() if torch.is_tensor(got) else np.asarray(got)
     return got.shape == want.shape and got.dtype == want.dtype and bool((got == want).all())
-
-
-def net(seed, c0, widths, relus=None, scale=1.0):
-    """Seeded layers [(W, b, relu)] of the given widths; every layer has ReLU
-    unless `relus` says otherwise."""
-    rng = np.random.default_rng(seed)
-    layers, c_in = [], c0
-    for k, c_out in enumerate(widths):
-        w = (rng.normal(size=(c_out, c_in)) * scale / np.sqrt(c_in)).astype(np.float32)
-        b = (rng.normal(size=c_out) * 0.2).astype(np.float32)
-        layers.append((w, b, True if relus is None else bool(relus[k])))
-        c_in = c_out
-    return layers
-
-
-def upload(layers):
-    from pandasim import CloudMlp
-
-    return CloudMlp(layers, DEV)
-
-
-def raw_mlp(sim, rows, mlp, pool=1, out=None, offset=0, expect=0):
-    """ps_cloud_mlp on a device tensor rows [B, R, C0]; -> out."""
-    from pandasim.sim import _ptr
-
-    nb, r, c0 = rows.shape
-    if out is None:
-        out = torch.full((nb, r // pool, mlp.widths[-1]), SENTINEL, device=DEV)
-    assert raw_call(sim, "ps_cloud_mlp", sim._ctx, _ptr(rows), r, c0, mlp.array, len(mlp), pool, _ptr(out), out.shape[2],
-               offset, sim._stream()) == expect
-    return out
-
-
-def raw_group_mlp(sim, xyz, feats, centre_idx, gidx, mlp, out=None, offset=0, expect=0):
-    from pandasim.sim import _ptr
-
-    nb, n = xyz.shape[:2]
-    d, (s, k) = 0 if feats is None else feats.shape[2], gidx.shape[1:]
-    if out is None:
-        out = torch.full((nb, s, mlp.widths[-1]), SENTINEL, device=DEV)
-    assert raw_call(sim, "ps_cloud_group_mlp", sim._ctx, _ptr(xyz), _ptr(feats), n, d, _ptr(centre_idx), s, _ptr(gidx), k,
-               mlp.array, len(mlp), _ptr(out), out.shape[2], offset, sim._stream()) == expect
-    return out
-
-
-def random_groups(seed, nb, n, s, k, d):
-    """A cloud with features and group indices padded as the ball query pads
-    them: each row's tail repeats its first index."""
-    rng = np.random.default_rng(seed)
-    xyz = rng.uniform(-1, 1, size=(nb, n, 3)).astype(np.float32)
-    feats = rng.normal(size=(nb, n, d)).astype(np.float32) if d else None
-    centre = np.stack([rng.permutation(n)[:s] for _ in range(nb)]).astype(np.int32)
-    gidx = np.sort(rng.integers(0, n, size=(nb, s, k)), axis=-1).astype(np.int32)
-    fill = rng.integers(1, k + 1, size=(nb, s))
-    for b in range(nb):
-        for c in range(s):
-            gidx[b, c, fill[b, c]:] = gidx[b, c, 0]  # duplicate rows
-    return xyz, feats, centre, gidx
 
 
 # ----------------------------------------------------- shapes against the restatement

@@ -10,7 +10,12 @@
  * Conventions
  *   - Every buffer argument is a DEVICE pointer owned by the caller (PyTorch
  *     tensors in panda-lang-manip_amd/pandasim); the library never allocates
- *     per call and holds no host-language objects.
+ *     per call and holds no host-language objects.  Two context-owned
+ *     scratch buffers are allocated on first use and freed by ps_destroy: the
+ *     ray-casting calls' render_prims (ps_render, ps_point_cloud,
+ *     ps_cloud_keypoint_features) and Stack's stash (ps_step, ps_step_oriented,
+ *     ps_sim_step, ps_motion_run); each is initialised on the stream of the
+ *     call that creates it.
  *   - Calls are asynchronous on the given HIP stream (hipStream_t passed as
  *     void*; NULL = default stream).  One ps_ctx per (process, device); a
  *     context is not re-entrant.

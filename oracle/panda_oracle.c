@@ -1613,8 +1613,9 @@ static void ulp_noise(double *x, int n) {
 /* Test hook (never part of the restated algorithm): each substep appends its
  * PGS iteration count to a caller buffer while one is set (serial use only;
  * scripts/pgs_iteration_stats.py). */
-/* Test hook (tests/parity_judge.py): the PGS exits k > 0 iterations after its
- * stopping rule is first met (capped at PM_SOLVER_ITERATIONS), or, k < 0, with
+/* Test hook (no test or probe of tests/parity_judge.py calls it; it served the
+ * replays of DESIGN.md §6, whose samples it does not explain): the PGS exits
+ * k > 0 iterations after its stopping rule is first met (capped at PM_SOLVER_ITERATIONS), or, k < 0, with
  * the impulses of the iteration before the one that met it.  The fp32 path's
  * exit test compares a rounded residual with 1e-7, so it can leave one
  * iteration apart from the fp64 oracle on any substep; for a statically

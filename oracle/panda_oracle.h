@@ -154,14 +154,17 @@ void po_mass_matrix(const po_config *cfg, const double q[9], double M[81]);
 void po_bias_forces(const po_config *cfg, const double q[9], const double qd[9], double h[9]);
 void po_link_inertia(int link, double inertia[3]);
 void po_set_link_aabb(int link, double lx, double ly, double lz);
-/* test hook: deliberate model errors for the parity classifier's power test
- * (tests/test_judge_power.py); PO_MUT_NONE restores the model, not thread-safe */
 /* test hook: the PGS exits k iterations after its stopping rule is met (k > 0) or
- * one iteration before (k < 0): parity_judge's stopping-rule probe; not thread-safe */
+ * one iteration before (k < 0).  No test or probe of parity_judge calls it: it
+ * served the replays of DESIGN.md §6 (round 6), where moving the exit by +-1-8
+ * iterations moved the resting-stack samples by <= 1e-3 rad/s against the GPU's
+ * 1.2e-2 rad/s, so it does not explain them; not thread-safe */
 void po_set_pgs_shift(int k);
 /* test hook: the box-box clip lines moved outward by m metres (parity_judge's
  * pair-order probe); not thread-safe */
 void po_set_clip_bias(double m);
+/* test hook: deliberate model errors for the parity classifier's power test
+ * (tests/test_judge_power.py); PO_MUT_NONE restores the model, not thread-safe */
 #define PO_MUT_NONE 0
 #define PO_MUT_MOTOR_KP 1     /* kp := PM_MOTOR_KP x value */
 #define PO_MUT_LINK_DAMPING 2 /* btMultiBody damping k1 = k2 of every body := value */

@@ -24,6 +24,18 @@ the end effector by 8e-4 m; the same holds at the upper limit
 alone (_ill_conditioned) and held to the loose bounds; every other sample to
 the tight ones, or to the tight ones plus the oracle's own sensitivity to the
 fp32 resolution of the state (_sensitivity).
+
+The verdict on a whole judged contact workload lives here too, as pure
+functions of the classified samples: contact_workload_failures (no beyond
+sample, the caps on the other classes) with its one escape, at_pgs_resolution
+(the velocities of a stack the oracle finds at rest -- stack_rest_evidence,
+stack_at_rest -- within the PGS stopping rule's resolution).
+test_gpu_parity.test_judged_contact_workloads asserts it on the GPU's samples;
+tests/test_judge_power.py requires it to fail on the stand-in's wrong models
+down to cube 2's mass x 1.002 -- which they do through their unexcused beyond
+samples alone, so those cases pin no constant -- and pins every bound and cap
+of it on synthetic samples at and just past each boundary
+(test_escape_boundaries, test_verdict_caps_at_896_samples).
 """
 import numpy as np
 
@@ -268,3 +280,102 @@ NOT_TIGHT_CAP = {"blocked": 0.005, "free": 0.08}
 
 def not_tight_cap(task):
     return NOT_TIGHT_CAP["free" if task in FREE_GRIPPER else "blocked"]
+
+
+# ------------------------------------------------------------------------
+# The verdict on a judged contact workload (test_gpu_parity.
+# test_judged_contact_workloads: Stack stack_push, Flip push, Stack push on
+# cube 1; 64 envs x 14 steps), as pure functions of the classified samples so
+# that the CPU suite runs wrong models through the very conditions the GPU
+# test asserts (tests/test_judge_power.py).
+#
+# The fp32 stand-in of tests/judge_power.py leaves 3.2 % (Stack) and 2.9 %
+# (Flip) of these samples conditioned and none beyond
+# (profiles/r06_judge_power.log); caps: 6 % conditioned, 8 % ill-conditioned,
+# 1 % ill-conditioned beyond the loose bounds (a cube balanced on an edge of
+# the other is a branch the oracle cannot resolve at fp32 resolution; where it
+# tips the two runs part by more than the loose bounds: round 6, stack_push
+# step 8 env 25).
+JUDGED_CONTACT_CAPS = {"conditioned": 0.06, "bif": 0.08}
+PAST_LOOSE_CAP = 0.01
+
+# Resting stacked cubes: a body's velocity after the solve is fixed only to
+# the PGS stopping rule's resolution (Bullet exits once every row's
+# (dl / dinv)^2 <= 1e-7: a last row velocity change of up to 3.2e-4 m/s,
+# 1.6e-2 rad/s over the cube's 0.02 m contact offsets), and each of the two
+# runs stops somewhere within it: twice that between them.  Replayed (round 6,
+# stack_push steps 2 and 5, envs 9 and 22: the oracle's own probes move them by
+# <= 1.4e-3 rad/s): positions and rotations agree to 3e-7 m / 2e-5 rad,
+# velocities part by at most 3.7e-4 m/s and 1.2e-2 rad/s.  Such samples (every
+# other group tight, the objects' velocities within 6.4e-4 m/s and 3.2e-2
+# rad/s) are counted apart, at most 0.5 %; no other beyond.
+PGS_RESOLUTION = {"_vel": 2 * 3.2e-4, "_avel": 2 * 1.6e-2}
+PGS_RESOLUTION_CAP = 0.005
+
+
+def at_pgs_resolution(task, errs, rest):
+    """True for a 'beyond' sample whose only disagreement is the objects'
+    velocities, within the PGS stopping rule's resolution (above), on a stack
+    the oracle alone finds at rest; `errs` are judge's per-group errors, `rest`
+    is stack_rest_evidence's."""
+    objv = [k for k in errs if k.startswith("obj") and k.endswith(("_vel", "_avel"))]
+    return stack_at_rest(rest) and all(v <= TOL[task][k] for k, v in errs.items() if k not in objv) and \
+        all(errs[k] <= PGS_RESOLUTION["_vel" if k.endswith("_vel") else "_avel"] for k in objv)
+
+
+def stack_rest_evidence(cfg, snap, i, action):
+    """What the oracle alone says about env i's step being a resting stack:
+    the cached cube-cube points after its own step, and the cubes' largest
+    speeds (m/s, rad/s) before and after it."""
+    e = oracle_env_from(cfg, snap, i)
+    O.step(cfg, e, action)
+    f = snap["f"][:, i]
+    v = max(max(np.linalg.norm(f[r + 7:r + 10]), np.linalg.norm(e.obj[b].vel[:])) for b, r in enumerate(OBJECT_ROWS))
+    w = max(max(np.linalg.norm(f[r + 10:r + 13]), np.linalg.norm(e.obj[b].omg[:])) for b, r in enumerate(OBJECT_ROWS))
+    return {"pair_after": int(e.cache.pair_n), "v": float(v), "w": float(w)}
+
+
+# The speeds below which the oracle's own cubes count as at rest: twice the
+# largest of the unmutated fp32 stand-in's resting samples.  Its 896 Stack
+# stack_push samples fall in two groups: 560 resting, up to 3.6e-4 m/s and
+# 8.4e-3 rad/s, and the pushed ones from 4.2e-2 m/s up.
+REST_SPEED = {"v": 2 * 3.6e-4, "w": 2 * 8.4e-3}
+
+
+def stack_at_rest(rest):
+    """The precondition of the derivation above, decided by the oracle alone
+    (stack_rest_evidence): the cubes touch after its step, and neither moves
+    faster than REST_SPEED before or after it."""
+    return rest["pair_after"] > 0 and rest["v"] <= REST_SPEED["v"] and rest["w"] <= REST_SPEED["w"]
+
+
+def groups_past_loose(errs):
+    """The groups of an ill-conditioned sample's errors beyond the loose bounds."""
+    return {k: v for k, v in errs.items() if v > LOOSE[k]}
+
+
+def contact_workload_failures(task, n, counts, beyond, past_loose, excuse=at_pgs_resolution):
+    """The verdict on a judged contact workload of n samples: the conditions it
+    breaks, one line each; [] passes.  counts: judge's class counts; beyond:
+    (step, env, errs, stack_rest_evidence) of every 'beyond' sample; past_loose: (step, env, ...) of
+    every 'bif' sample with an error past LOOSE.  No beyond sample but those
+    at the PGS resolution (`excuse`; the scan of scripts/judge_power_scan.py
+    also runs with none excused), those at most 0.5 %, and the caps above."""
+    resolution = [b for b in beyond if excuse(task, b[2], b[3])]
+    unexcused = [b for b in beyond if not excuse(task, b[2], b[3])]
+    fails = []
+    if unexcused:
+        fails.append(f"beyond: {len(unexcused)} of {len(beyond)} beyond samples are not at the PGS resolution: " +
+                     ", ".join(f"({b[0]}, {b[1]}, {_fmt(b[2])}, {b[3]})" for b in unexcused[:8]))
+    if len(resolution) > PGS_RESOLUTION_CAP * n:
+        fails.append(f"resolution: {len(resolution)} samples at the PGS resolution > {PGS_RESOLUTION_CAP * n:g}")
+    for cls, cap in JUDGED_CONTACT_CAPS.items():
+        if counts[cls] > cap * n:
+            fails.append(f"{cls}: {counts[cls]} > {cap * n:g}")
+    if len(past_loose) > PAST_LOOSE_CAP * n:
+        fails.append(f"past loose: {len(past_loose)} ill-conditioned samples past the loose bounds > {PAST_LOOSE_CAP * n:g}")
+    return fails
+
+
+def _fmt(errs):
+    return {k: f"{v:.1e}" for k, v in errs.items()}

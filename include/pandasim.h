@@ -319,6 +319,57 @@ int ps_plan_release(ps_ctx *ctx, const void *state, void *plan, const float *wid
  * task, either control type).  PS_ERR_ARG: a NULL buffer or max_steps < 1. */
 int ps_motion_run(ps_ctx *ctx, void *state, void *plan, int max_steps, void *stream);
 
+/* --- Motion programs: a sequence of primitives in one launch ---
+ *
+ * A program is num_segments segments, 1 to PS_PROGRAM_MAX_SEGMENTS; every env
+ * runs its own segments one after the other to the end, planning each from
+ * the state it has reached, without waiting for any other env. */
+enum {
+    PS_SEG_MOVE = 0,    /* Panda.move to goal_pos[s], goal_quat[s] */
+    PS_SEG_GRASP = 1,   /* Panda.grasp */
+    PS_SEG_RELEASE = 2, /* Panda.release of width[s] */
+    PS_SEG_WAIT = 3     /* wait_steps[s] times PyBullet.step (20 substeps), the motors as they stand */
+};
+#define PS_PROGRAM_MAX_SEGMENTS 32
+#define PS_PROGRAM_MAX_WAIT 1000 /* control steps of one wait segment, at least 1 */
+
+/* Runs the program in one launch; env i ends where the calls ps_plan_move /
+ * ps_plan_grasp / ps_plan_release + ps_motion_run to the plan's end, made
+ * segment by segment with the segments' masks, leave it, bit for bit.
+ *
+ * Host arrays, read before the call returns: kinds [S] (PS_SEG_*), wait_steps
+ * [S] (read for PS_SEG_WAIT only; may be NULL without one).  blocked0: the
+ * gripper's blocked flag before the first segment (the reference's
+ * block_gripper, which ps_plan_move's caller writes into the plan); a grasp
+ * sets it and a release clears it for the segments after it, in every env,
+ * whatever the masks are.
+ * Device arrays: goal_pos [S, B, 3] f32 world and goal_quat [S, B, 4] f32
+ * (x, y, z, w), row s read for a move; width [S, B] f32, row s read for a
+ * release, NULL = 1 for every release; mask [S, B] u8, NULL = all: env i runs
+ * segment s when mask[s, i] != 0.
+ *
+ * A wait uses the motor targets of the last control step this launch executed
+ * in that env, or the state's target rows when it is the env's first segment,
+ * with ps_step's gains and no inverse kinematics.  A move whose goal position
+ * or quaternion is not finite, or whose quaternion is zero, is not started:
+ * the env stops there and runs none of its later segments.  An env whose
+ * segments are all masked out, or which stops before its first control step,
+ * keeps its state and plan bits.
+ *
+ * completed [B] i32 (may be NULL): the index of the first segment not run, S
+ * when all ran (a masked-out segment counts as run); steps [B] i32 (may be
+ * NULL): the control steps executed.  On return the plan holds each env's
+ * last move, grasp or release that ran, with done == num_steps (a wait writes
+ * no plan row).  The motor gain rows are written as ps_motion_run writes them.
+ *
+ * PS_ERR_ARG, nothing launched or written: a NULL ctx, state, plan or kinds;
+ * num_segments out of range; an unknown kind; a wait without wait_steps or
+ * with a count outside 1 to PS_PROGRAM_MAX_WAIT; a move with a NULL goal_pos
+ * or goal_quat. */
+int ps_motion_program(ps_ctx *ctx, void *state, void *plan, int num_segments, const int32_t *kinds,
+                      const int32_t *wait_steps, int blocked0, const float *goal_pos, const float *goal_quat,
+                      const float *width, const uint8_t *mask, int32_t *completed, int32_t *steps, void *stream);
+
 /* --- pieces of the unfused (Robot/Task plugin) path, pandasim/core.py --- */
 
 #define PS_MAX_UNIFORM 8

@@ -2,7 +2,8 @@
 // batched Panda simulator: configuration, layout and context, the dimension
 // getters and the setters, and the entry points that dispatch to another
 // unit's launcher (ps_step, ps_step_oriented: step_kernels.hip; ps_sim_step:
-// sim_kernels.hip; ps_motion_run: motion_kernels.hip), with the diagnostic
+// sim_kernels.hip; ps_motion_run: motion_kernels.hip; ps_motion_program:
+// program_kernels.hip), with the diagnostic
 // builds' buffers.  No kernel lives here: every other entry point sits in
 // the unit of its kernel (state_kernels.hip, plan_kernels.hip,
 // render_kernels.hip).
@@ -261,6 +262,51 @@ int ps_motion_run(ps_ctx *c, void *state, void *plan, int max_steps, void *strea
     hipStream_t st = (hipStream_t)stream;
     if (ensure_stash(c, st) != PS_OK) return fail(c, PS_ERR_HIP, "hipMalloc of the Stack stash failed");
 #define PS_SCENE_LAUNCH(NOBJ, SHAPE) PS_MOTION_LAUNCHER_NAME(NOBJ, SHAPE)(c, state, plan, max_steps, st)
+    PS_FOR_EACH_SCENE(PS_SCENE_CASE)
+#undef PS_SCENE_LAUNCH
+    return fail(c, PS_ERR_UNSUPPORTED, "no kernel of this scene");
+}
+
+// every check before anything is enqueued (the Stack stash's memset
+// included); the host arrays are packed into the kernel's by-value argument,
+// the blocked flag of each segment as the sequence of Panda calls leaves it
+int ps_motion_program(ps_ctx *c, void *state, void *plan, int num_segments, const int32_t *kinds,
+                      const int32_t *wait_steps, int blocked0, const float *goal_pos, const float *goal_quat,
+                      const float *width, const uint8_t *mask, int32_t *completed, int32_t *steps, void *stream) {
+    if (!c || !state || !plan || !kinds) return fail(c, PS_ERR_ARG, "null argument");
+    if (num_segments < 1 || num_segments > PS_PROGRAM_MAX_SEGMENTS)
+        return fail(c, PS_ERR_ARG, "num_segments out of range");
+    ps_program_args prog;
+    memset(&prog, 0, sizeof prog);
+    prog.num_segments = num_segments;
+    bool blocked = blocked0 != 0;
+    for (int s = 0; s < num_segments; s++) {
+        const int k = kinds[s];
+        if (k == PS_SEG_MOVE) {
+            if (!goal_pos || !goal_quat) return fail(c, PS_ERR_ARG, "a move segment needs goal_pos and goal_quat");
+        } else if (k == PS_SEG_GRASP) {
+            blocked = true;
+        } else if (k == PS_SEG_RELEASE) {
+            blocked = false;
+        } else if (k == PS_SEG_WAIT) {
+            if (!wait_steps || wait_steps[s] < 1 || wait_steps[s] > PS_PROGRAM_MAX_WAIT)
+                return fail(c, PS_ERR_ARG, "a wait segment's count is out of range");
+            prog.wait[s] = (uint16_t)wait_steps[s];
+        } else {
+            return fail(c, PS_ERR_ARG, "unknown segment kind");
+        }
+        prog.kinds |= (uint64_t)k << (2 * s);
+        prog.blocked |= (uint32_t)blocked << s;
+    }
+    prog.goal_pos = goal_pos;
+    prog.goal_quat = goal_quat;
+    prog.width = width;
+    prog.mask = mask;
+    prog.completed = completed;
+    prog.steps = steps;
+    hipStream_t st = (hipStream_t)stream;
+    if (ensure_stash(c, st) != PS_OK) return fail(c, PS_ERR_HIP, "hipMalloc of the Stack stash failed");
+#define PS_SCENE_LAUNCH(NOBJ, SHAPE) PS_PROGRAM_LAUNCHER_NAME(NOBJ, SHAPE)(c, state, plan, prog, st)
     PS_FOR_EACH_SCENE(PS_SCENE_CASE)
 #undef PS_SCENE_LAUNCH
     return fail(c, PS_ERR_UNSUPPORTED, "no kernel of this scene");

@@ -9,11 +9,9 @@ namespace {
 
 // ------------------------------------------------------ motion primitives
 // Panda.move up to its loop (panda_cartesian.py:98-114): the plan of env i
-// from its state and goal, fp64 on the f32 state (FK of link 11 and the
-// rotation-matrix -> quaternion step as k_link_state)
+// from its state and goal (plan_move_rows, ps_motion.h)
 __global__ __launch_bounds__(kBlock) void k_plan_move(KParams P, PlanView pl, const float *goal_pos,
                                                       const float *goal_quat, const uint8_t *mask) {
-#pragma clang fp contract(off)
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.n) return;
     pl.I(PS_PLAN_DONE, i) = 0;
@@ -23,39 +21,11 @@ __global__ __launch_bounds__(kBlock) void k_plan_move(KParams P, PlanView pl, co
     }
     float q[9], qd[9];
     load_robot(P.s, i, q, qd);
-    Kin k;
-    fk(q, k);
-    const V3 pf = k.f[11].o + P.sc.base;
-    const Q4 qf = mat_to_quat(k.f[11].R);
-    const double start[3] = {(double)pf.x, (double)pf.y, (double)pf.z};
-    double tot[3], d2 = 0.0;
-    for (int c = 0; c < 3; c++) {
-        tot[c] = (double)goal_pos[i * 3 + c] - start[c];
-        d2 += tot[c] * tot[c];
-    }
-    const int num = move_num_steps(sqrt(d2));
-    for (int c = 0; c < 3; c++) {
-        pl.D(PS_PLAN_START + c, i) = start[c];
-        pl.D(PS_PLAN_DELTA + c, i) = tot[c] / (double)num;
-    }
-    pl.D(PS_PLAN_WIDTH, i) = (double)q[7] + (double)q[8];
-    const Q4d q0 = unit(Q4d{(double)qf.x, (double)qf.y, (double)qf.z, (double)qf.w});
-    const Q4d q1 = unit(Q4d{(double)goal_quat[i * 4], (double)goal_quat[i * 4 + 1], (double)goal_quat[i * 4 + 2],
-                            (double)goal_quat[i * 4 + 3]});
-    double rv[3];
-    relative_rotvec(q0, q1, rv);
-    pl.D(PS_PLAN_Q0, i) = q0.x;
-    pl.D(PS_PLAN_Q0 + 1, i) = q0.y;
-    pl.D(PS_PLAN_Q0 + 2, i) = q0.z;
-    pl.D(PS_PLAN_Q0 + 3, i) = q0.w;
-    for (int c = 0; c < 3; c++) pl.D(PS_PLAN_ROTVEC + c, i) = rv[c];
-    pl.I(PS_PLAN_NUM_STEPS, i) = num;
-    pl.I(PS_PLAN_KIND, i) = PS_PLAN_KIND_MOVE;
+    plan_move_rows(P.sc, pl, i, q, goal_pos, goal_quat);
 }
 
 // Panda.grasp / release up to their loops (panda_cartesian.py:124-126,
-// 139-141): 30 control steps of action (0, 0, 0, width) and the gripper's
-// blocked flag
+// 139-141; plan_hold_rows, ps_motion.h)
 __global__ __launch_bounds__(kBlock) void k_plan_hold(KParams P, PlanView pl, const float *width, int blocked,
                                                       const uint8_t *mask) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,26 +37,7 @@ __global__ __launch_bounds__(kBlock) void k_plan_hold(KParams P, PlanView pl, co
     }
     float q[9], qd[9];
     load_robot(P.s, i, q, qd);
-    Kin k;
-    fk(q, k);
-    const V3 pf = k.f[11].o + P.sc.base;
-    const Q4 qf = mat_to_quat(k.f[11].R);
-    const Q4d q0 = unit(Q4d{(double)qf.x, (double)qf.y, (double)qf.z, (double)qf.w});
-    pl.D(PS_PLAN_START, i) = (double)pf.x;
-    pl.D(PS_PLAN_START + 1, i) = (double)pf.y;
-    pl.D(PS_PLAN_START + 2, i) = (double)pf.z;
-    for (int c = 0; c < 3; c++) {
-        pl.D(PS_PLAN_DELTA + c, i) = 0.0;
-        pl.D(PS_PLAN_ROTVEC + c, i) = 0.0;
-    }
-    pl.D(PS_PLAN_WIDTH, i) = width ? (double)width[i] : 1.0;
-    pl.D(PS_PLAN_Q0, i) = q0.x;
-    pl.D(PS_PLAN_Q0 + 1, i) = q0.y;
-    pl.D(PS_PLAN_Q0 + 2, i) = q0.z;
-    pl.D(PS_PLAN_Q0 + 3, i) = q0.w;
-    pl.I(PS_PLAN_NUM_STEPS, i) = PS_PLAN_HOLD_STEPS;
-    pl.I(PS_PLAN_BLOCKED, i) = blocked;
-    pl.I(PS_PLAN_KIND, i) = PS_PLAN_KIND_HOLD;
+    plan_hold_rows(P.sc, pl, i, q, width, blocked);
 }
 
 }  // namespace

@@ -38,12 +38,25 @@ struct ps_step_io {
     const float *orn;  // ps_step_oriented: [B, 4] target quaternions (x, y, z, w); NULL in ps_step
 };
 
+// ps_motion_program's program as its kernel takes it, by value: the checked
+// host arrays packed (ps_motion_program, pandasim.hip) and the device arrays
+struct ps_program_args {
+    int32_t num_segments;
+    uint32_t blocked;  // bit s: the gripper's blocked flag while segment s runs
+    uint64_t kinds;    // two bits per segment: PS_SEG_*
+    uint16_t wait[PS_PROGRAM_MAX_SEGMENTS];  // control steps of a wait segment
+    const float *goal_pos, *goal_quat, *width;  // [S, B, 3], [S, B, 4], [S, B] (width: or NULL)
+    const uint8_t *mask;                        // [S, B] or NULL
+    int32_t *completed, *steps;                 // [B] or NULL
+};
+
 // The sets the library is built over, each written once here and once in
 // pandasim/build.py (TASKS, GROUP_TASKS, SCENES), as the numerals the
 // launcher names and the units' -D defines carry:
 //   tasks (PS_TASK_*), those with 16- and 8-lane group kernels first -- Stack
 //   (4: two objects, 21 DoFs) has none;
-//   scenes of the plugin path and the motion primitives, (objects, shape).
+//   scenes of the plugin path, the motion primitives and the motion
+//   programs, (objects, shape).
 #define PS_FOR_EACH_GROUP_TASK(X) X(0) X(1) X(2) X(3) X(5)
 #define PS_FOR_EACH_TASK(X) PS_FOR_EACH_GROUP_TASK(X) X(4)
 #define PS_FOR_EACH_SCENE(X) X(0, 0) X(1, 0) X(1, 1) X(2, 0)
@@ -68,19 +81,24 @@ struct ps_step_io {
 // ps_motion_run's kernel of each scene (motion_kernels.hip)
 #define PS_MOTION_LAUNCHER_NAME_(NOBJ, SHAPE) ps_launch_motion_##NOBJ##_##SHAPE
 #define PS_MOTION_LAUNCHER_NAME(NOBJ, SHAPE) PS_MOTION_LAUNCHER_NAME_(NOBJ, SHAPE)
+// ps_motion_program's kernel of each scene (program_kernels.hip)
+#define PS_PROGRAM_LAUNCHER_NAME_(NOBJ, SHAPE) ps_launch_program_##NOBJ##_##SHAPE
+#define PS_PROGRAM_LAUNCHER_NAME(NOBJ, SHAPE) PS_PROGRAM_LAUNCHER_NAME_(NOBJ, SHAPE)
 
 typedef int ps_step_launcher(ps_ctx *c, void *state, const ps_step_io &io, int lanes, hipStream_t st);
 typedef int ps_step_group_launcher(ps_ctx *c, const void *params, const ps_step_io &io, int lanes, hipStream_t st);
 typedef int ps_sim_launcher(ps_ctx *c, void *state, int n_substeps, hipStream_t st);
 typedef int ps_motion_launcher(ps_ctx *c, void *state, void *plan, int max_steps, hipStream_t st);
+typedef int ps_program_launcher(ps_ctx *c, void *state, void *plan, const ps_program_args &prog, hipStream_t st);
 #define PS_DECLARE_STEP_LAUNCHERS(T) \
     ps_step_launcher PS_STEP_LAUNCHER_NAME(T, 0), PS_STEP_LAUNCHER_NAME(T, 1), PS_STEP_ORI_LAUNCHER_NAME(T);
 #define PS_DECLARE_STEP_GROUP_LAUNCHERS(T)                                                        \
     ps_step_group_launcher PS_STEP_GROUP_LAUNCHER_NAME(T, 0), PS_STEP_GROUP_LAUNCHER_NAME(T, 1), \
         PS_STEP_ORI_GROUP_LAUNCHER_NAME(T);
-#define PS_DECLARE_SCENE_LAUNCHERS(NOBJ, SHAPE)           \
-    ps_sim_launcher PS_SIM_LAUNCHER_NAME(NOBJ, SHAPE); \
-    ps_motion_launcher PS_MOTION_LAUNCHER_NAME(NOBJ, SHAPE);
+#define PS_DECLARE_SCENE_LAUNCHERS(NOBJ, SHAPE)               \
+    ps_sim_launcher PS_SIM_LAUNCHER_NAME(NOBJ, SHAPE);       \
+    ps_motion_launcher PS_MOTION_LAUNCHER_NAME(NOBJ, SHAPE); \
+    ps_program_launcher PS_PROGRAM_LAUNCHER_NAME(NOBJ, SHAPE);
 // (the group launchers are declared for every task and defined for the group
 // tasks: a pair's launcher names its own behind `if constexpr (task_has_groups)`)
 PS_FOR_EACH_TASK(PS_DECLARE_STEP_LAUNCHERS)

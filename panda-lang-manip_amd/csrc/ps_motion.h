@@ -1,9 +1,11 @@
 // ps_motion.h — the Cartesian motion primitives of panda_cartesian.py:53-145
-// (move / grasp / release): the plan buffer's view, the arithmetic of one
-// control step and the fused run kernel k_motion.  motion_kernels.hip
+// (move / grasp / release): the plan buffer's view, the plans of one env
+// (plan_move_rows, plan_hold_rows), the arithmetic of one control step
+// (motion_control_step) and the fused run kernel k_motion.  motion_kernels.hip
 // instantiates k_motion once per scene, as sim_kernels.hip does k_sim_step
 // (its launchers are declared with the others, ps_ctx.h); plan_kernels.hip
 // holds the plan kernels and their entry points, pandasim.hip ps_motion_run.
+// ps_motion_program.h runs a whole sequence of primitives on the same pieces.
 #pragma once
 
 #include "ps_env.h"
@@ -78,6 +80,72 @@ PS_D int move_num_steps(double d) {
     return (int)fl + (mod > 1e-3 ? 1 : 0);
 }
 
+// Panda.move up to its loop (panda_cartesian.py:98-114): the plan of env i
+// from its joint positions q and its goal (goal_pos[i * 3 ..], goal_quat[i * 4
+// ..]), fp64 on the f32 state (FK of link 11 and the rotation-matrix ->
+// quaternion step as k_link_state); every row but done and blocked.  Returns
+// num_steps.  k_plan_move and k_motion_program plan with it.
+PS_D int plan_move_rows(const Scene &sc, const PlanView &pl, int64_t i, const float q[9], const float *goal_pos,
+                        const float *goal_quat) {
+#pragma clang fp contract(off)
+    Kin k;
+    fk(q, k);
+    const V3 pf = k.f[11].o + sc.base;
+    const Q4 qf = mat_to_quat(k.f[11].R);
+    const double start[3] = {(double)pf.x, (double)pf.y, (double)pf.z};
+    double tot[3], d2 = 0.0;
+    for (int c = 0; c < 3; c++) {
+        tot[c] = (double)goal_pos[i * 3 + c] - start[c];
+        d2 += tot[c] * tot[c];
+    }
+    const int num = move_num_steps(sqrt(d2));
+    for (int c = 0; c < 3; c++) {
+        pl.D(PS_PLAN_START + c, i) = start[c];
+        pl.D(PS_PLAN_DELTA + c, i) = tot[c] / (double)num;
+    }
+    pl.D(PS_PLAN_WIDTH, i) = (double)q[7] + (double)q[8];
+    const Q4d q0 = unit(Q4d{(double)qf.x, (double)qf.y, (double)qf.z, (double)qf.w});
+    const Q4d q1 = unit(Q4d{(double)goal_quat[i * 4], (double)goal_quat[i * 4 + 1], (double)goal_quat[i * 4 + 2],
+                            (double)goal_quat[i * 4 + 3]});
+    double rv[3];
+    relative_rotvec(q0, q1, rv);
+    pl.D(PS_PLAN_Q0, i) = q0.x;
+    pl.D(PS_PLAN_Q0 + 1, i) = q0.y;
+    pl.D(PS_PLAN_Q0 + 2, i) = q0.z;
+    pl.D(PS_PLAN_Q0 + 3, i) = q0.w;
+    for (int c = 0; c < 3; c++) pl.D(PS_PLAN_ROTVEC + c, i) = rv[c];
+    pl.I(PS_PLAN_NUM_STEPS, i) = num;
+    pl.I(PS_PLAN_KIND, i) = PS_PLAN_KIND_MOVE;
+    return num;
+}
+
+// Panda.grasp / release up to their loops (panda_cartesian.py:124-126,
+// 139-141): 30 control steps of action (0, 0, 0, width) and the gripper's
+// blocked flag; every row but done.  k_plan_hold's and k_motion_program's.
+PS_D void plan_hold_rows(const Scene &sc, const PlanView &pl, int64_t i, const float q[9], const float *width,
+                         int blocked) {
+    Kin k;
+    fk(q, k);
+    const V3 pf = k.f[11].o + sc.base;
+    const Q4 qf = mat_to_quat(k.f[11].R);
+    const Q4d q0 = unit(Q4d{(double)qf.x, (double)qf.y, (double)qf.z, (double)qf.w});
+    pl.D(PS_PLAN_START, i) = (double)pf.x;
+    pl.D(PS_PLAN_START + 1, i) = (double)pf.y;
+    pl.D(PS_PLAN_START + 2, i) = (double)pf.z;
+    for (int c = 0; c < 3; c++) {
+        pl.D(PS_PLAN_DELTA + c, i) = 0.0;
+        pl.D(PS_PLAN_ROTVEC + c, i) = 0.0;
+    }
+    pl.D(PS_PLAN_WIDTH, i) = width ? (double)width[i] : 1.0;
+    pl.D(PS_PLAN_Q0, i) = q0.x;
+    pl.D(PS_PLAN_Q0 + 1, i) = q0.y;
+    pl.D(PS_PLAN_Q0 + 2, i) = q0.z;
+    pl.D(PS_PLAN_Q0 + 3, i) = q0.w;
+    pl.I(PS_PLAN_NUM_STEPS, i) = PS_PLAN_HOLD_STEPS;
+    pl.I(PS_PLAN_BLOCKED, i) = blocked;
+    pl.I(PS_PLAN_KIND, i) = PS_PLAN_KIND_HOLD;
+}
+
 // The action and target orientation of control step `istep` (1-based) of env
 // i's plan, from the joint positions q: move's waypoint and slerp
 // (panda_cartesian.py:116-120) or grasp/release's hold with the ee link's
@@ -110,6 +178,59 @@ PS_D void motion_step_target(const Scene &sc, const PlanView &pl, int64_t i, int
     if (t[2] < 0.0) t[2] = 0.0;
     target = mk((float)t[0], (float)t[1], (float)t[2]);
     a_width = (float)fmin(fmax(w, -1.0), 1.0);
+}
+
+// One control step of env i, k_motion's and k_motion_program's: the plan's
+// target for step `istep` (1-based) of `num`, IK, the motor targets (kept in
+// tgt), then PM_SUBSTEPS substeps (run_substeps, which carries the contact
+// cache).  The plan rows are read here, at every control step (the index goes
+// through an empty asm so the loads stay in the caller's loop), instead of
+// occupying 28 registers through the solver.  HOLD_TARGETS (k_motion_program's
+// wait segments): with `hold` the targets in tgt stand as they are, no IK.
+template <int NOBJ, int SHAPE, bool HOLD_TARGETS>
+PS_D void motion_control_step(const KParams &P, const PlanView &pl, int64_t i, int istep, int num, int kind,
+                              bool blocked, bool hold, float q[9], float qd[9], Body *bd, const MJStore &lds,
+                              float tgt[9] PS_PROF_PARAM) {
+    int64_t ii = i;
+    asm volatile("" : "+v"(ii));
+    if (!HOLD_TARGETS || !hold) {
+        Kin k;
+        fk(q, k);
+        V3 t;
+        Q4 orn;
+        float aw;
+        motion_step_target(P.sc, pl, ii, istep, num, kind, k, t, orn, aw);
+        float qik[9];
+        inverse_kinematics<11>(q, t - P.sc.base, orn, qik);
+#pragma unroll
+        for (int d = 0; d < 7; d++) tgt[d] = qik[d];
+        const float width = blocked ? 0.0f : (q[7] + q[8]) + aw;
+        tgt[7] = tgt[8] = width * 0.5f;
+    }
+    run_substeps<NOBJ, SHAPE, true>(P, i, PM_SUBSTEPS, q, qd, bd, lds, true, tgt PS_PROF_ARG);
+}
+
+// What a motion kernel leaves in the state: robot, bodies, the motor targets
+// of its last control step and ps_step's gains
+template <int NOBJ>
+PS_D void store_motion_state(const StateView &s, int64_t i, const float q[9], const float qd[9], const Body *bd,
+                             const float tgt[9]) {
+    {
+        Motors m;
+#pragma unroll
+        for (int d = 0; d < 9; d++) {
+            m.target[d] = tgt[d];
+            m.kp[d] = (float)PM_MOTOR_KP;
+            m.kd[d] = (float)PM_MOTOR_KD;
+            m.vel[d] = 0.0f;
+            m.imp[d] = (float)(joint_force(d) * PM_TIMESTEP);
+        }
+        store_motor_targets(s, i, m);
+        store_motor_gains(s, i, m);
+    }
+    store_robot(s, i, q, qd);
+#pragma unroll
+    for (int b = 0; b < NOBJ; b++) store_body(s, i, b, bd[b]);
 }
 
 // ps_motion_run: up to max_steps control steps of every env whose plan has
@@ -148,44 +269,10 @@ __global__ __launch_bounds__(kBlock, 1) void k_motion(KParams P, PlanView pl, in
     for (int k = 0; k < PS_ITP_WORDS; k++) pt.itp[k] = 0;
 #endif
     float tgt[9];
-    for (int st = 0; st < todo; st++) {
-        // the plan rows are re-read at every control step (the index goes
-        // through an empty asm so the loads stay in the loop) instead of
-        // occupying 28 registers through the solver
-        int64_t ii = i;
-        asm volatile("" : "+v"(ii));
-        {
-            Kin k;
-            fk(q, k);
-            V3 t;
-            Q4 orn;
-            float aw;
-            motion_step_target(P.sc, pl, ii, done + 1 + st, num, kind, k, t, orn, aw);
-            float qik[9];
-            inverse_kinematics<11>(q, t - P.sc.base, orn, qik);
-#pragma unroll
-            for (int d = 0; d < 7; d++) tgt[d] = qik[d];
-            const float width = blocked ? 0.0f : (q[7] + q[8]) + aw;
-            tgt[7] = tgt[8] = width * 0.5f;
-        }
-        run_substeps<NOBJ, SHAPE, true>(P, i, PM_SUBSTEPS, q, qd, bd, lds, true, tgt PS_PROF_ARG);
-    }
-    {
-        Motors m;
-#pragma unroll
-        for (int d = 0; d < 9; d++) {
-            m.target[d] = tgt[d];
-            m.kp[d] = (float)PM_MOTOR_KP;
-            m.kd[d] = (float)PM_MOTOR_KD;
-            m.vel[d] = 0.0f;
-            m.imp[d] = (float)(joint_force(d) * PM_TIMESTEP);
-        }
-        store_motor_targets(s, i, m);
-        store_motor_gains(s, i, m);
-    }
-    store_robot(s, i, q, qd);
-#pragma unroll
-    for (int b = 0; b < NOBJ; b++) store_body(s, i, b, bd[b]);
+    for (int st = 0; st < todo; st++)
+        motion_control_step<NOBJ, SHAPE, false>(P, pl, i, done + 1 + st, num, kind, blocked, false, q, qd, bd, lds,
+                                                tgt PS_PROF_ARG);
+    store_motion_state<NOBJ>(s, i, q, qd, bd, tgt);
     pl.I(PS_PLAN_DONE, i) = done + todo;
 #ifdef PS_PROFILE_PHASES
     // the diagnostic build's phase counters, as k_step adds them (lane 0 of

@@ -2,7 +2,7 @@
 
 Host layer over libpandasim.so (HIP, gfx950).  See DESIGN.md.
 """
-from . import panda_cartesian
+from . import panda_cartesian, skills
 from ._lib import PandasimError, lib
 from .cloudnet import CloudMlp, CloudSegNet, DecodedWaypoints, fold_batchnorm, round_bfloat16
 from .core import PyBulletRobot, RobotTaskEnv, Task, TimeLimit
@@ -15,5 +15,6 @@ from .tasks import Flip, PickAndPlace, Push, Reach, Slide, Stack
 
 __all__ = ["make", "PandaVecEnv", "PandaSim", "GRASP_VIEWS", "keypoint_features_args", "patch_size", "project_to_pixels", "CloudMlp", "fold_batchnorm", "round_bfloat16", "CloudSegNet", "DecodedWaypoints", "REGISTRY", "PandasimError", "lib", "PyBulletRobot",
            "Task", "RobotTaskEnv", "TimeLimit", "Panda", "Reach", "Push", "PickAndPlace", "PandaReachEnv",
-           "PandaPushEnv", "PandaPickAndPlaceEnv", "Slide", "Stack", "Flip", "PandaSlideEnv", "PandaStackEnv", "PandaFlipEnv", "panda_cartesian"]
+           "PandaPushEnv", "PandaPickAndPlaceEnv", "Slide", "Stack", "Flip", "PandaSlideEnv", "PandaStackEnv", "PandaFlipEnv", "panda_cartesian",
+           "skills"]
 __version__ = "0.1.0"

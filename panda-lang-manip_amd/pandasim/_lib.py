@@ -103,7 +103,8 @@ F, D = P(C.c_float), P(C.c_double)
 # waypoint decoding (PandaSim.decode_waypoints), "keypoint" the keypoint
 # conditioning of the cloud's feature rows (PandaSim.keypoint_features),
 # "bfloat" the shared MLP's learned layers in reduced precision (bfloat16 operands
-# on the bf16 matrix cores: CloudMlp(..., precision="bfloat16")).
+# on the bf16 matrix cores: CloudMlp(..., precision="bfloat16")), "program" a
+# whole sequence of motion primitives in one launch (PandaSim.motion_program).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -143,6 +144,7 @@ SIGNATURES = {
     "ps_plan_grasp": ([V, V, V, V, V], I, "motion"),
     "ps_plan_release": ([V, V, V, V, V, V], I, "motion"),
     "ps_motion_run": ([V, V, V, I, V], I, "motion"),
+    "ps_motion_program": ([V, V, V, I, P(C.c_int32), P(C.c_int32), I, V, V, V, V, V, V, V], I, "program"),
     "ps_cloud_workspace_bytes": ([I64, I, I, I], I64, "cloud"),
     "ps_point_cloud": ([V, V, V, I, I, I, P(Visual), V, V, I, C.c_uint64, V, V, V, V, V, V], I, "cloud"),
     "ps_cloud_normalize": ([V, V, I, V, V, V, V], I, "group"),
@@ -163,6 +165,7 @@ SIGNATURES = {
 }
 ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
 MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
+PROGRAM_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "program")
 CLOUD_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "cloud")
 GROUP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "group")
 PROPAGATE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "propagate")
@@ -187,6 +190,9 @@ def exported_symbols():
 PLAN_START, PLAN_DELTA, PLAN_WIDTH, PLAN_Q0, PLAN_ROTVEC, PLAN_NUM_F64_ROWS = 0, 3, 6, 7, 11, 14
 PLAN_NUM_STEPS, PLAN_DONE, PLAN_BLOCKED, PLAN_KIND, PLAN_NUM_I32_ROWS = 0, 1, 2, 3, 4
 PLAN_KIND_MOVE, PLAN_KIND_HOLD, PLAN_HOLD_STEPS = 0, 1, 30
+# the segments of a motion program (PS_SEG_*, PS_PROGRAM_*)
+SEG_MOVE, SEG_GRASP, SEG_RELEASE, SEG_WAIT = 0, 1, 2, 3
+PROGRAM_MAX_SEGMENTS, PROGRAM_MAX_WAIT = 32, 1000
 
 
 def check_fresh(path: str) -> None:

@@ -7,7 +7,8 @@ kernels of each (task, control) pair (step_kernels.hip: the one-lane kernel,
 the oriented step's kernels of each task at ee control (the same source with
 -DPS_STEP_ORI=1: 6 + 5 objects), the plugin-path substep kernel of each scene
 (sim_kernels.hip, 4 objects), the motion primitives' kernel of each scene
-(motion_kernels.hip, 4 objects), and the small kernels with the entry points
+(motion_kernels.hip, 4 objects), the motion programs' kernel of each scene
+(program_kernels.hip, 4 objects), and the small kernels with the entry points
 that launch them, one object per subject: state init / reset / queries / rng /
 reward / Euler conversion (state_kernels.hip), the motion plans
 (plan_kernels.hip), camera, ray caster and deprojection (render_kernels.hip),
@@ -61,7 +62,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-f
 # The sets the units are built over, each once here and once in csrc/ps_ctx.h
 # (PS_FOR_EACH_TASK, PS_FOR_EACH_GROUP_TASK, PS_FOR_EACH_SCENE): the tasks of
 # include/pandasim.h, those with group kernels (not Stack, 4) and the scenes
-# (objects, shape) of the plugin path and the motion primitives.
+# (objects, shape) of the plugin path, the motion primitives and programs.
 TASKS = (0, 1, 2, 3, 4, 5)
 GROUP_TASKS = (0, 1, 2, 3, 5)
 SCENES = ((0, 0), (1, 0), (1, 1), (2, 0))
@@ -84,6 +85,9 @@ UNITS = ([("pandasim", "pandasim.hip", [])]
             for n, s in SCENES]
          # ps_motion_run's kernel of each scene (k_motion, ps_motion.h): 4 objects
          + [(f"motion_{n}_{s}", "motion_kernels.hip", [f"-DPS_MOTION_NOBJ={n}", f"-DPS_MOTION_SHAPE={s}"])
+            for n, s in SCENES]
+         # ps_motion_program's kernel of each scene (k_motion_program, ps_motion_program.h): 4 objects
+         + [(f"program_{n}_{s}", "program_kernels.hip", [f"-DPS_PROGRAM_NOBJ={n}", f"-DPS_PROGRAM_SHAPE={s}"])
             for n, s in SCENES]
          # the small kernels with their entry points, by subject
          + [("state_kernels", "state_kernels.hip", []), ("plan_kernels", "plan_kernels.hip", []),

@@ -848,6 +848,27 @@ class PandaSim(CloudNet):
         """ps_motion_run: every env runs min(max_steps, num_steps - done) control steps."""
         self._call("ps_motion_run", self._ctx, _ptr(self.state), _ptr(plan.buf), int(max_steps), self._stream())
 
+    def motion_program(self, plan: "MotionPlan", program, blocked: bool):
+        """ps_motion_program: the segments of `program` (a
+        panda_cartesian.MotionProgram of this batch) in one launch, each env
+        planning its next segment from the state it has reached; `blocked` is
+        the gripper's flag before the first segment.  The goals' Euler angles
+        become quaternions in one euler_xyz_to_quat call.  Returns (completed
+        [B] i32, steps [B] i32, the flag after the last segment); no tensor is
+        read on the host."""
+        if program.num_envs != self.num_envs or program.device != self.device:
+            raise ValueError(f"program: built for {program.num_envs} envs on {program.device}, the sim has "
+                             f"{self.num_envs} on {self.device}")
+        low = program.lower(blocked)
+        S, B = len(low.kinds), self.num_envs
+        quat = None if low.goal_euler is None else self.euler_xyz_to_quat(low.goal_euler)
+        completed = torch.empty(B, dtype=torch.int32, device=self.device)
+        steps = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._call("ps_motion_program", self._ctx, _ptr(self.state), _ptr(plan.buf), S, (C.c_int32 * S)(*low.kinds),
+                   (C.c_int32 * S)(*low.wait_steps), int(bool(blocked)), _ptr(low.goal_pos), _ptr(quat), _ptr(low.width),
+                   _ptr(low.mask), _ptr(completed), _ptr(steps), self._stream())
+        return completed, steps, low.blocked_after
+
 
 class MotionPlan:
     """The plan buffer of the motion primitives (include/pandasim.h PS_PLAN_*):

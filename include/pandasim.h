@@ -864,6 +864,127 @@ int ps_cloud_keypoint_features(ps_ctx *ctx, const void *state, const ps_cloud_vi
                                const uint8_t *colors, const int32_t *count, int K, float *feats, int ld,
                                int out_offset, double *targets, void *stream);
 
+/* --- Device-resident HER replay --- */
+
+/* stable-baselines3's HerReplayBuffer for the context's B envs
+ * (examples/train_push.py: DDPG(..., replay_buffer_class=HerReplayBuffer); the
+ * env's compute_reward, core.py:226, is what it relabels with), in one
+ * caller-owned device buffer: one launch stores a step of all envs, one call
+ * samples a batch with the `future` or `final` hindsight goals and their
+ * rewards recomputed, without a host synchronisation.  The host counts the
+ * stores (n_stores) and passes scalars; no device counter is read back.
+ *
+ *   Ring.      capacity = T time slots of B envs.  A store writes slot
+ *              pos = n_stores mod T of every env; stored = min(n_stores, T).
+ *              A transition is one row of row_floats 32-bit words, padded to a
+ *              multiple of 16 bytes, rows laid out [T][B][row]: obs[O], ag[G],
+ *              dg[G], action[A], next_obs[O], next_ag[G], reward (f32),
+ *              terminated (0 / 1 in a 32-bit word) and ep_end (i32: the slot of
+ *              the last transition of the row's episode, -1 while it runs), at
+ *              the word offsets ps_replay_layout names.  Beside the ring, per
+ *              env: cur_len (i32; slots of the running episode, saturating at
+ *              T) and the pending obs / ag / dg of the transition that the next
+ *              store completes (rows of pending_floats words, [B][pending]).
+ *   begin.     After a reset: records the pending observation of the masked
+ *              envs (all with mask NULL).  A masked env with cur_len > 0 (a
+ *              reset in mid-episode) has its running episode closed at its last
+ *              stored slot, (pos_next - 1) mod T, as an episode's end below;
+ *              then cur_len = 0.
+ *   store.     Per env b: (1) slot pos takes the pending obs / ag / dg, the
+ *              action, next_obs = final_obs[b], next_ag = final_ag[b] (obs[b] and
+ *              ag[b] with final_obs NULL: auto-reset off), reward, terminated and
+ *              ep_end = -1; (2) cur_len = min(cur_len + 1, T); (3) with
+ *              terminated | truncated, ep_end of the last cur_len slots (from
+ *              pos backwards, mod T) becomes pos, then cur_len = 0; (4) pending
+ *              becomes obs / ag / dg.  ps_step leaves the pre-reset observation
+ *              of every env in final_obs, so the last transition of an episode
+ *              never holds the next episode's first observation.  An episode
+ *              longer than T overwrites its own oldest slots; cur_len
+ *              saturates, so the back-fill never walks more than T slots and
+ *              every T >= 1 is legal.
+ *   Valid.     Env b has v_b = stored - cur_len[b] valid transitions: the v_b
+ *              oldest slots from oldest = (pos_next - stored) mod T, the j-th
+ *              at slot (oldest + j) mod T; each has ep_end >= 0.  V is the sum
+ *              of v_b and P the inclusive prefix sum of v over the envs.
+ *   sample.    For sample i of M, in integers only (u64, wrapping):
+ *                mix(z): z += 0x9E3779B97F4A7C15;
+ *                        z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                        z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+ *                h = mix(mix(seed) ^ draw); w_k = mix(h ^ (4 i + k)), k = 0, 1, 2
+ *                r = mulhi64(w_0, V)                the rank among the valid
+ *                b = the least env with P[b] > r; j = r - (P[b] - v_b)
+ *                t = (oldest + j) mod T
+ *                relabel = (w_1 >> 32) < her_threshold
+ *                n = ((ep_end[t, b] - t) mod T) + 1
+ *                future: g = (t + mulhi64(w_2, n)) mod T;  final: g = ep_end[t, b]
+ *              obs, ag, action, next_obs, next_ag and terminated are those of
+ *              slot (t, b).  Not relabelled, dg and reward are the stored ones
+ *              and goal_slot = -1; relabelled, dg = next_ag[g, b], goal_slot = g
+ *              and reward is the task's compute_reward of (next_ag[t, b], dg) in
+ *              ps_compute_reward's f32 / f32 arithmetic.  success is is_success
+ *              of (next_ag[t, b], dg) of every sample, in that arithmetic.
+ *              mulhi64's bias is below V / 2^64; there is no rejection.  With
+ *              V = 0 every output is zero, except env_idx = slot = goal_slot =
+ *              -1.  n_valid[0] = V.  The same (seed, draw, buffer) gives the
+ *              same batch; a caller counts draw up per call.
+ *
+ * The caller's buffer is ps_replay_layout.bytes long and 16-byte aligned (rows
+ * and pending rows are moved by 128-bit words; every section of the layout
+ * starts at a multiple of 256 bytes).  pos, pos_next and stored must be those
+ * of the buffer's own history of stores: the range checks below cannot tell a
+ * consistent pair that belongs to another history, and with such scalars a
+ * sample's indices are unspecified -- the kernel keeps them inside the ring
+ * (a slot index is clamped to 0..T-1, an ep_end outside 0..T-1 counts as the
+ * slot itself), so nothing is read out of bounds, and nothing else is promised.
+ *
+ * The buffer holds the prefix sum's workspace too, so ps_replay_sample writes
+ * that part of an otherwise read buffer, and two samples of one buffer must
+ * not run concurrently.  Every call is ordered on the caller's stream: no
+ * synchronisation, no default-stream work.  Limits (PS_ERR_ARG before anything
+ * is enqueued, the buffer untouched): NULL ctx, replay or required pointer; a
+ * replay pointer that is not 16-byte aligned;
+ * capacity outside 1..PS_REPLAY_MAX_CAPACITY or more than PS_REPLAY_MAX_ENVS
+ * envs; pos or pos_next outside 0..capacity-1; stored outside 0..capacity (and
+ * pos_next != stored while stored < capacity); stored = 0 on sample; M outside
+ * 1..PS_REPLAY_MAX_BATCH; an unknown strategy; her_threshold > 2^32. */
+#define PS_REPLAY_MAX_CAPACITY (1 << 20)
+#define PS_REPLAY_MAX_ENVS (1 << 20) /* one second-level scan block of 1 024 first-level blocks */
+#define PS_REPLAY_MAX_BATCH (1LL << 27)
+enum { PS_REPLAY_FUTURE = 0, PS_REPLAY_FINAL = 1 };
+
+/* Byte offsets from the replay pointer and word offsets within a row. */
+typedef struct ps_replay_layout {
+    int64_t bytes; /* of the whole buffer */
+    int64_t ring_offset, cur_len_offset, pending_offset, prefix_offset, block_sum_offset;
+    int32_t capacity, num_envs, row_floats, pending_floats;
+    int32_t obs_dim, goal_dim, action_dim;
+    int32_t off_obs, off_ag, off_dg, off_action, off_next_obs, off_next_ag, off_reward, off_terminated, off_ep_end;
+} ps_replay_layout;
+
+/* Outputs of a sample, device pointers: obs [M, O], ag / dg / next_ag [M, G],
+ * action [M, A], next_obs [M, O], reward [M] f32, terminated / success /
+ * relabelled [M] u8, env_idx / slot / goal_slot [M] i32, n_valid [1] i64.  Any
+ * may be NULL except obs, action and dg. */
+typedef struct ps_replay_batch {
+    float *obs, *ag, *dg, *action, *next_obs, *next_ag, *reward;
+    uint8_t *terminated, *success, *relabelled;
+    int32_t *env_idx, *slot, *goal_slot;
+    int64_t *n_valid;
+} ps_replay_batch;
+
+/* needs no GPU */
+int ps_replay_layout_of(const ps_ctx *ctx, int capacity, ps_replay_layout *out);
+/* the whole buffer zero, every ep_end = -1 */
+int ps_replay_init(ps_ctx *ctx, void *replay, int capacity, void *stream);
+int ps_replay_begin(ps_ctx *ctx, void *replay, int capacity, int pos_next, int stored, const float *obs,
+                    const float *ag, const float *dg, const uint8_t *mask, void *stream);
+int ps_replay_store(ps_ctx *ctx, void *replay, int capacity, int pos, const float *actions, const float *obs,
+                    const float *ag, const float *dg, const float *final_obs, const float *final_ag,
+                    const float *reward, const uint8_t *terminated, const uint8_t *truncated, void *stream);
+int ps_replay_sample(ps_ctx *ctx, const void *replay, int capacity, int pos_next, int stored, int strategy,
+                     uint64_t seed, uint64_t draw, uint64_t her_threshold, int64_t M, const ps_replay_batch *out,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 // env (or one row) per lane; every kernel reads/writes the
 // structure-of-arrays state with coalesced row accesses.  No substep here.
 #include "ps_ctx.h"
+#include "ps_reward.h"
 #include "ps_task.h"
 
 namespace {
@@ -166,45 +167,25 @@ __global__ __launch_bounds__(kBlock) void k_base_state(KParams P, int b, float *
 
 // compute_reward / is_success for HER (core.py:226): goal pairs of `gd`
 // values; f64 arithmetic when either side is f64 (numpy promotion), f32
-// otherwise (threshold rounded to f32)
+// otherwise (threshold rounded to f32): ps_reward.h, shared with the replay
+// sampler
 __global__ __launch_bounds__(256) void k_compute_reward(int task, int reward_type, const void *ag, int ag_dbl,
                                                         const void *dg, int dg_dbl, float *reward, uint8_t *success,
                                                         int64_t n) {
-#pragma clang fp contract(off)
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int gd = task == PS_TASK_STACK ? 6 : (task == PS_TASK_FLIP ? 4 : 3);
-    const bool angle = task == PS_TASK_FLIP;
-    const double thr = task == PS_TASK_STACK ? PM_STACK_DISTANCE_THRESHOLD
-                       : angle                ? PM_FLIP_DISTANCE_THRESHOLD
-                                              : PM_DISTANCE_THRESHOLD;
+    const int gd = goal_pair_dim(task);
+    float r;
+    bool ok;
     if (ag_dbl || dg_dbl) {
-        double m = 0.0;
-        for (int k = 0; k < gd; k++) {
-            double a = ag_dbl ? ((const double *)ag)[i * gd + k] : (double)((const float *)ag)[i * gd + k];
-            double g = dg_dbl ? ((const double *)dg)[i * gd + k] : (double)((const float *)dg)[i * gd + k];
-            double e = __dsub_rn(a, g);
-            double t = angle ? opaque(__dmul_rn(a, g)) : opaque(__dmul_rn(e, e));
-            m = k == 0 ? t : __dadd_rn(m, t);
-        }
-        double d = angle ? __dsub_rn(1.0, opaque(__dmul_rn(m, m))) : __dsqrt_rn(m);
-        if (reward) reward[i] = reward_for(reward_type, d, thr);
-        if (success) success[i] = d < thr;
+        const void *a = ag_dbl ? (const void *)((const double *)ag + i * gd) : (const void *)((const float *)ag + i * gd);
+        const void *g = dg_dbl ? (const void *)((const double *)dg + i * gd) : (const void *)((const float *)dg + i * gd);
+        goal_pair_reward_f64(task, reward_type, a, ag_dbl, g, dg_dbl, r, ok);
     } else {
-        const float *a = (const float *)ag, *g = (const float *)dg;
-        float m = 0.0f;
-        for (int k = 0; k < gd; k++) {
-            float av = a[i * gd + k], gv = g[i * gd + k];
-            float e = __fsub_rn(av, gv);
-            float t = angle ? opaque(__fmul_rn(av, gv)) : opaque(__fmul_rn(e, e));
-            m = k == 0 ? t : __fadd_rn(m, t);
-        }
-        // correctly rounded f32 root: the f64 root rounded once
-        float d = angle ? __fsub_rn(1.0f, opaque(__fmul_rn(m, m))) : __double2float_rn(__dsqrt_rn((double)m));
-        float tf = (float)thr;
-        if (reward) reward[i] = reward_type == 0 ? (d > tf ? -1.0f : -0.0f) : -d;
-        if (success) success[i] = d < tf;
+        goal_pair_reward_f32(task, reward_type, (const float *)ag + i * gd, (const float *)dg + i * gd, r, ok);
     }
+    if (reward) reward[i] = r;
+    if (success) success[i] = ok;
 }
 
 

@@ -9,6 +9,7 @@ from .core import PyBulletRobot, RobotTaskEnv, Task, TimeLimit
 from .envs import REGISTRY, PandaVecEnv, make
 from .panda_tasks import (PandaFlipEnv, PandaPickAndPlaceEnv, PandaPushEnv, PandaReachEnv, PandaSlideEnv,
                           PandaStackEnv)
+from .replay import HerReplay, ReplaySample
 from .robots import Panda
 from .sim import GRASP_VIEWS, PandaSim, keypoint_features_args, patch_size, project_to_pixels
 from .tasks import Flip, PickAndPlace, Push, Reach, Slide, Stack
@@ -16,5 +17,5 @@ from .tasks import Flip, PickAndPlace, Push, Reach, Slide, Stack
 __all__ = ["make", "PandaVecEnv", "PandaSim", "GRASP_VIEWS", "keypoint_features_args", "patch_size", "project_to_pixels", "CloudMlp", "fold_batchnorm", "round_bfloat16", "CloudSegNet", "DecodedWaypoints", "REGISTRY", "PandasimError", "lib", "PyBulletRobot",
            "Task", "RobotTaskEnv", "TimeLimit", "Panda", "Reach", "Push", "PickAndPlace", "PandaReachEnv",
            "PandaPushEnv", "PandaPickAndPlaceEnv", "Slide", "Stack", "Flip", "PandaSlideEnv", "PandaStackEnv", "PandaFlipEnv", "panda_cartesian",
-           "skills"]
+           "skills", "HerReplay", "ReplaySample"]
 __version__ = "0.1.0"

@@ -74,6 +74,22 @@ VISUAL_SPHERE = 2
 ROLES = ("plane", "table", "object1", "object2", "target1", "target2", "robot", "background")
 
 
+class ReplayLayout(C.Structure):
+    """ps_replay_layout: byte offsets into the replay buffer, word offsets into a row."""
+    _fields_ = ([(n, C.c_int64) for n in ("bytes", "ring_offset", "cur_len_offset", "pending_offset", "prefix_offset",
+                                          "block_sum_offset")]
+                + [(n, C.c_int32) for n in ("capacity", "num_envs", "row_floats", "pending_floats", "obs_dim",
+                                            "goal_dim", "action_dim", "off_obs", "off_ag", "off_dg", "off_action",
+                                            "off_next_obs", "off_next_ag", "off_reward", "off_terminated",
+                                            "off_ep_end")])
+
+
+class ReplayBatch(C.Structure):
+    """ps_replay_batch: the outputs of a sample (device pointers; NULL skips one)."""
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "ag", "dg", "action", "next_obs", "next_ag", "reward", "terminated",
+                                          "success", "relabelled", "env_idx", "slot", "goal_slot", "n_valid")]
+
+
 class Layout(C.Structure):
     _fields_ = [
         ("num_envs", C.c_int64), ("stride", C.c_int64), ("float_offset", C.c_int64), ("goal_offset", C.c_int64),
@@ -104,7 +120,8 @@ F, D = P(C.c_float), P(C.c_double)
 # conditioning of the cloud's feature rows (PandaSim.keypoint_features),
 # "bfloat" the shared MLP's learned layers in reduced precision (bfloat16 operands
 # on the bf16 matrix cores: CloudMlp(..., precision="bfloat16")), "program" a
-# whole sequence of motion primitives in one launch (PandaSim.motion_program).
+# whole sequence of motion primitives in one launch (PandaSim.motion_program),
+# "replay" the device-resident HER replay buffer (pandasim.replay.HerReplay).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -162,6 +179,11 @@ SIGNATURES = {
     "ps_cloud_decode_waypoints": ([V, V, I, I, I, V, V, V, C.c_uint32, C.c_uint32, V, V, V, V, V, V, V], I, "decode"),
     "ps_cloud_keypoint_features": ([V, V, P(CloudView), I, I, P(Visual), V, V, I, I, C.c_double, F, V, V, V, I, V, I, I, V,
                                     V], I, "keypoint"),
+    "ps_replay_layout_of": ([V, I, P(ReplayLayout)], I, "replay"),
+    "ps_replay_init": ([V, V, I, V], I, "replay"),
+    "ps_replay_begin": ([V, V, I, I, I, V, V, V, V, V], I, "replay"),
+    "ps_replay_store": ([V, V, I, I, V, V, V, V, V, V, V, V, V, V], I, "replay"),
+    "ps_replay_sample": ([V, V, I, I, I, I, C.c_uint64, C.c_uint64, C.c_uint64, I64, P(ReplayBatch), V], I, "replay"),
 }
 ORIENTED_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "oriented")
 MOTION_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "motion")
@@ -173,6 +195,9 @@ MLP_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "mlp")
 BFLOAT_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "bfloat")
 DECODE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "decode")
 KEYPOINT_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "keypoint")
+REPLAY_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "replay")
+REPLAY_FUTURE, REPLAY_FINAL = 0, 1
+REPLAY_MAX_CAPACITY, REPLAY_MAX_ENVS, REPLAY_MAX_BATCH, REPLAY_SCAN_BLOCK = 1 << 20, 1 << 20, 1 << 27, 1024
 CLOUD_MAX_VIEWS = 8
 CLOUD_MAX_POINTS, CLOUD_MAX_SCALES, CLOUD_MAX_FEATURES = 8192, 4, 16
 CLOUD_MAX_PROP_FEATURES, CLOUD_MAX_DENSE_POINTS = 2048, 1 << 20

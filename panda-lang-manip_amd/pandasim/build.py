@@ -18,7 +18,8 @@ propagation (propagate_kernels.hip), the shared MLP with max-pool on the f32
 matrix cores (mlp_kernels.hip) and in bfloat16 on the bf16 ones
 (mlp_bfloat_kernels.hip), the policy's waypoint decoding
 (decode_kernels.hip), the keypoint conditioning of the cloud's feature rows
-(keypoint_kernels.hip).
+(keypoint_kernels.hip), the device-resident HER replay buffer: fused store,
+prefix sum and relabelling sampler (replay_kernels.hip).
 
 Every object is compiled with the same flags (-O3, no -mllvm scheduler
 options).  Round 3 built the group kernels at -O1 after an -O2/-O3 miscompute
@@ -95,7 +96,7 @@ UNITS = ([("pandasim", "pandasim.hip", [])]
             ("group_kernels", "group_kernels.hip", []), ("propagate_kernels", "propagate_kernels.hip", []),
             ("mlp_kernels", "mlp_kernels.hip", []), ("decode_kernels", "decode_kernels.hip", []),
             ("keypoint_kernels", "keypoint_kernels.hip", []),
-            ("mlp_bfloat_kernels", "mlp_bfloat_kernels.hip", [])])
+            ("mlp_bfloat_kernels", "mlp_bfloat_kernels.hip", []), ("replay_kernels", "replay_kernels.hip", [])])
 
 # diagnostic variants (never loaded by the product unless PANDASIM_LIB names them)
 VARIANTS = {"": [], "prof": ["-DPS_PROFILE_PHASES"]}

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Register, scratch and LDS use of every step, motion, render and point-cloud kernel of a built object or
+"""Register, scratch and LDS use of every step, motion, render, point-cloud and replay kernel of a built object or
 library, from the code objects' AMDGPU metadata (no GPU needed).
 
 usage: python scripts/kernel_resources.py [lib or .o ...] [--json out.json]
@@ -100,7 +100,7 @@ def main(argv):
         for p in paths:
             for co in code_objects(p, tmp):
                 for k, v in kernels(co).items():
-                    if any(n in k for n in ("k_step", "k_sim_step", "k_motion", "k_render", "k_deproject", "k_cloud")):
+                    if any(n in k for n in ("k_step", "k_sim_step", "k_motion", "k_render", "k_deproject", "k_cloud", "k_replay")):
                         table[demangle(k)] = v
     for k, v in sorted(table.items()):
         print(f"{k:40s} vgpr {v.get('vgpr_count', 0):3d} agpr {v.get('agpr_count', 0):3d} "

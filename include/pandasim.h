@@ -804,6 +804,105 @@ int ps_cloud_decode_waypoints(ps_ctx *ctx, const float *head, int N, int ld, int
                               float *waypoints, float *quats, float *euler_deg, int32_t *counts, int32_t *labels,
                               int32_t *first_idx, void *stream);
 
+/* --- Point-cloud policy: demonstration labels and losses --- */
+
+/* The ground-truth side of the policy, forward only: the per-point targets a
+ * demonstration gives (task_classes/generate_combined_dset.py:422-484, record,
+ * with the normalisation of data_utils/PourDataLoader_cls_off.py:43-45) and the
+ * value of the reference's losses on them (models/model_cls_off_rot.py:63-79).
+ * Both work on the context's B clouds of N points, ordered on `stream`; all
+ * pointers are device memory, addressed with 64-bit offsets.  No atomics on
+ * floating-point values and nothing shared between clouds: the bits of cloud
+ * b depend on nothing but cloud b's inputs.
+ *
+ * ps_cloud_waypoint_labels is the inverse of ps_cloud_decode_waypoints: its
+ * 14 target columns are the columns the head carries behind its logits.
+ *
+ * Inputs.  points [B, N, 3] f32 the world points, xyz [B, N, 3] f32 the
+ * normalised ones, centroid [B, 3] and scale [B] f32 as ps_cloud_normalize
+ * wrote them, waypoints [B, 2, 3] f32 in the world (start, then end), quats
+ * [B, 2, 4] f32 xyzw (written through unchanged), radius (the reference's is
+ * 0.125), count [B] i32 or NULL (ps_point_cloud's M_b).  Set 0 below is the
+ * start set, set 1 the end set.
+ *
+ *   Distance.   d2(p, w), the f32 squared distance above, of the world point
+ *               and the world waypoint.  r2 = (float)radius * (float)radius,
+ *               one rounded f32 product, computed on the host.  The point is
+ *               in set k iff d2(p, w_k) <= r2: not strictly, as sklearn's
+ *               radius_neighbors; a NaN distance is in no set.
+ *   Class.      0 in neither set, 1 in the start set only, 2 in the end set
+ *               only, 3 in both.
+ *   Waypoint.   wn_k = (w_k - centroid) / scale per component in f32, both
+ *               operations rounded: ps_cloud_normalize's expression, so a
+ *               waypoint equal to a cloud point normalises to that point's xyz
+ *               bit for bit.
+ *   Targets.    The offset of set k is xyz - wn_k (f32) where the point is in
+ *               set k, else 0; the quaternion of set k is quats[b, k] where
+ *               the point is in set k, else 0.  A point of class 3 carries
+ *               both offsets, which is what Inference.predict's union1d reads
+ *               back.  (The one deviation: record()'s own three-column offsets
+ *               array, which predates the six-column head, leaves the points
+ *               of class 3 at zero.)
+ *   Zero scale. A cloud whose scale is not > 0 gets zero offsets, not NaN;
+ *               classes and quaternions as above.
+ *   Empty.      With count given, a cloud whose count is 0 gets cls -1 at
+ *               every point and zeros in its target columns.
+ *
+ * Outputs.  cls [B, N] i32; target [B, N, ld] f32, of which the columns
+ * out_offset .. out_offset + 13 are written (start offset 3, end offset 3,
+ * start quaternion 4, end quaternion 4) and the others left.
+ *
+ * Limits (PS_ERR_ARG, nothing launched, outputs untouched): a NULL required
+ * pointer, N outside 1..PS_CLOUD_MAX_DENSE_POINTS, a radius that is not
+ * positive and finite, out_offset < 0 or out_offset + 14 > ld, ld above
+ * PS_CLOUD_LABEL_MAX_LD. */
+#define PS_CLOUD_LABEL_MAX_LD 4096
+#define PS_CLOUD_LABEL_COLUMNS 14
+
+int ps_cloud_waypoint_labels(ps_ctx *ctx, const float *points, const float *xyz, const float *centroid,
+                             const float *scale, const float *waypoints, const float *quats, double radius,
+                             const int32_t *count, int N, int32_t *cls, float *target, int ld, int out_offset,
+                             void *stream);
+
+/* The forward value of the reference's losses (F.nll_loss on the class
+ * log-softmax, nn.L1Loss on the offsets and quaternions) as per-cloud sums,
+ * with the counts that turn them into means, and the accuracy's.
+ *
+ * Inputs.  head [B, N, ld] f32 with nc classes, as ps_cloud_decode_waypoints
+ * takes it; cls [B, N] i32 the true classes; target [B, N, ld_t] f32 whose
+ * columns target_offset .. target_offset + 13 are ps_cloud_waypoint_labels';
+ * start_mask / end_mask as ps_cloud_decode_waypoints takes them, here applied
+ * to the TRUE class.
+ *
+ *   Skipped.    A point whose cls is outside 0..nc-1 is skipped everywhere:
+ *               that is how -1 means "ignore".
+ *   NLL.        Of a point: the logits widened to f64; m = x[0], and for
+ *               c = 1 .. nc-1 ascending m = x[c] if x[c] > m;
+ *               nll = (m + log(sum over c ascending of exp(x[c] - m))) - x[cls].
+ *               A NaN logit makes that cloud's NLL sum NaN and nothing else.
+ *   L1.         |head - target| in f64 from the f32 operands (exact), summed
+ *               over the 3 (4) offset (quaternion) columns of set k at each
+ *               point whose true class is in set k.
+ *   Prediction. ps_cloud_decode_waypoints' Label rule.
+ *   Sums.       Every f64 sum in ps_cloud_decode_waypoints' fixed order: thread
+ *               t of T = 1024 takes points t, t + T, ... ascending (a point's
+ *               columns ascending), the T partial sums are added by halving.
+ *
+ * Outputs.  sums [B, 5] f64: the NLL, |d| of the start offsets, of the end
+ * offsets, of the start quaternions, of the end quaternions.  counts [B, 4]
+ * i32: the labelled (not skipped) points, those whose true class is in the
+ * start set, in the end set, and those whose predicted class equals cls.
+ * confusion [B, nc, nc] i32 or NULL: true class x predicted class.
+ *
+ * Limits (PS_ERR_ARG, nothing launched, outputs untouched): a NULL required
+ * pointer, N outside 1..PS_CLOUD_MAX_DENSE_POINTS, nc outside
+ * 2..PS_CLOUD_DECODE_MAX_CLASSES, ld outside nc + 14 .. PS_CLOUD_DECODE_MAX_LD,
+ * target_offset < 0 or target_offset + 14 > ld_t, ld_t above
+ * PS_CLOUD_LABEL_MAX_LD, a mask that is zero or has a bit at or above nc. */
+int ps_cloud_policy_loss(ps_ctx *ctx, const float *head, int N, int ld, int nc, const int32_t *cls,
+                         const float *target, int ld_t, int target_offset, uint32_t start_mask, uint32_t end_mask,
+                         double *sums, int32_t *counts, int32_t *confusion, void *stream);
+
 /* --- Point-cloud policy: keypoint conditioning --- */
 
 /* The fourth feature channel of the reference's inp_dim = 7 policies

@@ -22,7 +22,7 @@
 // its 16 waves cost no occupancy that a second workgroup would have used.
 #include <limits.h>
 
-#include "ps_ctx.h"
+#include "ps_cloud_math.h"
 
 namespace {
 
@@ -47,15 +47,7 @@ __global__ __launch_bounds__(kDecodeThreads) void k_cloud_decode(const float *he
     int cnt0 = 0, cnt1 = 0, first0 = INT_MAX, first1 = INT_MAX;
     for (int i = t; i < n; i += kDecodeThreads) {
         const float *row = rows + (int64_t)i * ld;
-        float best = row[0];
-        int label = 0;
-        for (int c = 1; c < nc; c++) {
-            const float v = row[c];
-            if (v > best) {
-                best = v;
-                label = c;
-            }
-        }
+        const int label = cloud_argmax(row, nc);
         if (labels) labels[env * n + i] = label;
         const bool in0 = (mask0 >> label) & 1u, in1 = (mask1 >> label) & 1u;
         if (in0 || in1) {

@@ -121,7 +121,9 @@ F, D = P(C.c_float), P(C.c_double)
 # "bfloat" the shared MLP's learned layers in reduced precision (bfloat16 operands
 # on the bf16 matrix cores: CloudMlp(..., precision="bfloat16")), "program" a
 # whole sequence of motion primitives in one launch (PandaSim.motion_program),
-# "replay" the device-resident HER replay buffer (pandasim.replay.HerReplay).
+# "replay" the device-resident HER replay buffer (pandasim.replay.HerReplay),
+# "labels" the policy's demonstration labels and the forward value of its
+# losses (PandaSim.label_cloud / policy_loss).
 SIGNATURES = {
     "ps_abi_version": (None, I, None),
     "ps_default_config": ([I, I, I, P(Config)], I, None),
@@ -179,6 +181,8 @@ SIGNATURES = {
     "ps_cloud_decode_waypoints": ([V, V, I, I, I, V, V, V, C.c_uint32, C.c_uint32, V, V, V, V, V, V, V], I, "decode"),
     "ps_cloud_keypoint_features": ([V, V, P(CloudView), I, I, P(Visual), V, V, I, I, C.c_double, F, V, V, V, I, V, I, I, V,
                                     V], I, "keypoint"),
+    "ps_cloud_waypoint_labels": ([V, V, V, V, V, V, V, C.c_double, V, I, V, V, I, I, V], I, "labels"),
+    "ps_cloud_policy_loss": ([V, V, I, I, I, V, V, I, I, C.c_uint32, C.c_uint32, V, V, V, V], I, "labels"),
     "ps_replay_layout_of": ([V, I, P(ReplayLayout)], I, "replay"),
     "ps_replay_init": ([V, V, I, V], I, "replay"),
     "ps_replay_begin": ([V, V, I, I, I, V, V, V, V, V], I, "replay"),
@@ -196,6 +200,7 @@ BFLOAT_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "bfloat")
 DECODE_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "decode")
 KEYPOINT_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "keypoint")
 REPLAY_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "replay")
+LABELS_SYMBOLS = tuple(n for n, s in SIGNATURES.items() if s[2] == "labels")
 REPLAY_FUTURE, REPLAY_FINAL = 0, 1
 REPLAY_MAX_CAPACITY, REPLAY_MAX_ENVS, REPLAY_MAX_BATCH, REPLAY_SCAN_BLOCK = 1 << 20, 1 << 20, 1 << 27, 1024
 CLOUD_MAX_VIEWS = 8
@@ -204,6 +209,7 @@ CLOUD_MAX_PROP_FEATURES, CLOUD_MAX_DENSE_POINTS = 2048, 1 << 20
 CLOUD_MLP_MAX_LAYERS, CLOUD_MLP_MAX_HIDDEN, CLOUD_MLP_MAX_LAST = 4, 512, 1024
 CLOUD_DECODE_MAX_CLASSES, CLOUD_DECODE_MAX_LD = 16, 4096
 CLOUD_KEYPOINT_MAX, CLOUD_KEYPOINT_MAX_RADIUS, CLOUD_KEYPOINT_MAX_LD = 4, 8, 4096
+CLOUD_LABEL_MAX_LD, CLOUD_LABEL_COLUMNS = 4096, 14
 
 
 def exported_symbols():

@@ -19,7 +19,8 @@ matrix cores (mlp_kernels.hip) and in bfloat16 on the bf16 ones
 (mlp_bfloat_kernels.hip), the policy's waypoint decoding
 (decode_kernels.hip), the keypoint conditioning of the cloud's feature rows
 (keypoint_kernels.hip), the device-resident HER replay buffer: fused store,
-prefix sum and relabelling sampler (replay_kernels.hip).
+prefix sum and relabelling sampler (replay_kernels.hip), the policy's
+demonstration labels and the forward value of its losses (label_kernels.hip).
 
 Every object is compiled with the same flags (-O3, no -mllvm scheduler
 options).  Round 3 built the group kernels at -O1 after an -O2/-O3 miscompute
@@ -96,7 +97,8 @@ UNITS = ([("pandasim", "pandasim.hip", [])]
             ("group_kernels", "group_kernels.hip", []), ("propagate_kernels", "propagate_kernels.hip", []),
             ("mlp_kernels", "mlp_kernels.hip", []), ("decode_kernels", "decode_kernels.hip", []),
             ("keypoint_kernels", "keypoint_kernels.hip", []),
-            ("mlp_bfloat_kernels", "mlp_bfloat_kernels.hip", []), ("replay_kernels", "replay_kernels.hip", [])])
+            ("mlp_bfloat_kernels", "mlp_bfloat_kernels.hip", []), ("replay_kernels", "replay_kernels.hip", []),
+            ("label_kernels", "label_kernels.hip", [])])
 
 # diagnostic variants (never loaded by the product unless PANDASIM_LIB names them)
 VARIANTS = {"": [], "prof": ["-DPS_PROFILE_PHASES"]}

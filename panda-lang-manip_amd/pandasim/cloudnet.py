@@ -1,10 +1,13 @@
 """The batched PointNet++ layer over a point-cloud observation:
 sampling and grouping, feature propagation, the shared MLP with max-pool, and
-the policy they compose: the network's forward and the waypoint decoding.
+the policy they compose: the network's forward and the waypoint decoding; and
+(§11.10) the policy's ground-truth side, forward only: a demonstration's
+per-point labels and the value of the losses against them.
 
 ``CloudNet`` is a mixin of ``PandaSim``; the checkers, ``GroupedCloud``,
-``CloudMlp``, ``fold_batchnorm``, ``CloudSegNet`` and ``DecodedWaypoints``
-beside it need no simulator at all.
+``CloudMlp``, ``fold_batchnorm``, ``CloudSegNet``, ``DecodedWaypoints``,
+``CloudLabels``, ``PolicyLoss`` and ``demonstration_records`` beside it need
+no simulator at all.
 """
 from __future__ import annotations
 
@@ -20,7 +23,8 @@ from ._lib import _ptr
 class CloudNet:
     """group_cloud, propagate_features, shared_mlp, abstract_features and, on top
     of them, segment_cloud, decode_waypoints and predict_waypoints for B
-    clouds.  They read no simulator state.  The host class provides exactly
+    clouds; label_cloud, policy_loss and evaluate_policy hold a network
+    against a demonstration.  They read no simulator state.  The host class provides exactly
     ``self.num_envs`` (B), ``self.device`` (a torch.device), ``self._ctx`` (a
     library context of B envs on that device), ``self._call(name, *args)``
     (the library call, raising on its error code) and ``self._stream()`` (the
@@ -241,6 +245,96 @@ class CloudNet:
         with that cloud's centroid and scale."""
         head, g1 = self.segment_cloud(net, points, colors, seed)
         return self.decode_waypoints(head, g1.xyz, net.num_classes, g1.centroid, g1.scale)
+
+    def label_cloud(self, points, waypoints, quats, radius: float = 0.125, group=None, count=None) -> "CloudLabels":
+        """The training targets a demonstration gives every env's cloud
+        (generate_combined_dset.py:422-484, record, with the loader's
+        normalisation of the waypoints, PourDataLoader_cls_off.py:43-45) --
+        fused (ps_cloud_waypoint_labels), on the device: per point the class
+        (0 neither, 1 within `radius` of the start waypoint, 2 of the end
+        waypoint, 3 of both; the distance is not strict) and the 14 columns
+        the head carries behind its logits: start offset (3) and end offset
+        (3), normalised point - normalised waypoint where the point is in that
+        set, else 0; start and end quaternion (4 + 4), `quats` where the point
+        is in that set, else 0.  A point of class 3 carries both.
+
+        points [B, N, 3] f32 in the world, waypoints [B, 2, 3] f32 in the world
+        (start, end), quats [B, 2, 4] f32 xyzw, count None or [B] i32
+        (point_cloud()'s "count": a cloud whose count is 0 gets class -1, which
+        policy_loss ignores, and zero targets).  group None normalises the
+        cloud here (ps_cloud_normalize, N <= CLOUD_MAX_POINTS); or the
+        GroupedCloud segment_cloud returned for these points, whose xyz,
+        centroid and scale are then used.  Returns a CloudLabels."""
+        B, dev = self.num_envs, self.device
+        points, waypoints, quats = (torch.as_tensor(t, device=dev) for t in (points, waypoints, quats))
+        if count is not None:
+            count = torch.as_tensor(count, device=dev)
+        N, radius = waypoint_labels_args(B, points, waypoints, quats, radius, group, count)
+        points, waypoints, quats = points.contiguous(), waypoints.contiguous(), quats.contiguous()
+        count = None if count is None else count.contiguous()
+        out = CloudLabels()
+        if group is None:
+            out.xyz = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+            out.centroid = torch.empty(B, 3, dtype=torch.float32, device=dev)
+            out.scale = torch.empty(B, dtype=torch.float32, device=dev)
+            self._call("ps_cloud_normalize", self._ctx, _ptr(points), N, _ptr(out.xyz), _ptr(out.centroid),
+                       _ptr(out.scale), self._stream())
+        else:
+            out.xyz, out.centroid, out.scale = group.xyz.contiguous(), group.centroid.contiguous(), group.scale.contiguous()
+        out.cls = torch.empty(B, N, dtype=torch.int32, device=dev)
+        out.target = torch.empty(B, N, L.CLOUD_LABEL_COLUMNS, dtype=torch.float32, device=dev)
+        self._call("ps_cloud_waypoint_labels", self._ctx, _ptr(points), _ptr(out.xyz), _ptr(out.centroid),
+                   _ptr(out.scale), _ptr(waypoints), _ptr(quats), radius, _ptr(count), N, _ptr(out.cls),
+                   _ptr(out.target), L.CLOUD_LABEL_COLUMNS, 0, self._stream())
+        return out
+
+    def policy_loss(self, head, cls, target, num_classes: int, start_classes=(1, 3), end_classes=(2, 3),
+                    return_confusion: bool = False) -> "PolicyLoss":
+        """The forward value of the reference's losses
+        (model_cls_off_rot.py:63-79: F.nll_loss on the class log-softmax,
+        nn.L1Loss on the offsets and the quaternions) of a head against
+        label_cloud's targets -- fused (ps_cloud_policy_loss), with the
+        accuracy; no backward pass.  A point whose cls is not a class (-1) is
+        ignored everywhere.  The L1 terms run over the points whose TRUE class
+        is in the start (end) set.
+
+        head [B, N, ld] f32 with ld >= num_classes + 14, cls [B, N] i32,
+        target [B, N, 14] f32.  Returns a PolicyLoss of device tensors; nothing
+        here waits for the device."""
+        B, dev = self.num_envs, self.device
+        head, cls, target = (torch.as_tensor(t, device=dev) for t in (head, cls, target))
+        N, ld, nc, ld_t, masks = policy_loss_args(B, head, cls, target, num_classes, start_classes, end_classes)
+        head, cls, target = head.contiguous(), cls.contiguous(), target.contiguous()
+        out = PolicyLoss()
+        out.sums = torch.empty(B, 5, dtype=torch.float64, device=dev)
+        out.counts = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        out.confusion = torch.empty(B, nc, nc, dtype=torch.int32, device=dev) if return_confusion else None
+        self._call("ps_cloud_policy_loss", self._ctx, _ptr(head), N, ld, nc, _ptr(cls), _ptr(target), ld_t, 0, masks[0],
+                   masks[1], _ptr(out.sums), _ptr(out.counts), _ptr(out.confusion), self._stream())
+        s, c = out.sums.sum(0), out.counts.sum(0).to(torch.float64)
+        rows = c[1] + c[2]
+        out.cls_loss = s[0] / c[0]
+        out.offset_loss = (s[1] + s[2]) / (3.0 * rows)
+        out.rot_loss = (s[3] + s[4]) / (4.0 * rows)
+        out.accuracy = c[3] / c[0]
+        return out
+
+    def evaluate_policy(self, net: "CloudSegNet", points, colors, waypoints, quats, radius: float = 0.125,
+                        seed: int = 0, count=None) -> "PolicyEvaluation":
+        """A network against a demonstration, for every env: segment_cloud,
+        label_cloud on that cloud's normalisation, policy_loss, and
+        decode_waypoints with the distance of each decoded waypoint from the
+        true one.  colors is what segment_cloud takes ([B, N, C - 3] f32:
+        the colours, or keypoint_features' rows).  Returns a PolicyEvaluation."""
+        head, g1 = self.segment_cloud(net, points, colors, seed)
+        out = PolicyEvaluation()
+        out.head = head
+        out.labels = self.label_cloud(points, waypoints, quats, radius, g1, count)
+        out.loss = self.policy_loss(head, out.labels.cls, out.labels.target, net.num_classes)
+        out.decoded = self.decode_waypoints(head, g1.xyz, net.num_classes, g1.centroid, g1.scale)
+        truth = torch.as_tensor(waypoints, device=self.device).to(torch.float32)
+        out.waypoint_error = torch.linalg.vector_norm(out.decoded.waypoints - truth, dim=-1)
+        return out
 
 
 class GroupedCloud:
@@ -598,6 +692,135 @@ def decode_waypoints_args(num_envs: int, head, xyz, num_classes, centroid, scale
         _want("decode_waypoints", "centroid", centroid, (B, 3))
         _want("decode_waypoints", "scale", scale, (B,))
     return N, ld, nc, (_class_mask("start_classes", start_classes, nc), _class_mask("end_classes", end_classes, nc))
+
+
+# ------------------------------------------------- the labels and the losses
+class CloudLabels:
+    """PandaSim.label_cloud's result: cls [B, N] i32 (0 neither set, 1 start, 2
+    end, 3 both; -1 at every point of an empty cloud), target [B, N, 14] f32
+    (start offset 3, end offset 3, start quaternion 4, end quaternion 4: the
+    head's columns behind its logits), and the normalisation the offsets are
+    in: xyz [B, N, 3], centroid [B, 3], scale [B] f32."""
+
+    __slots__ = ("cls", "target", "xyz", "centroid", "scale")
+
+
+class PolicyLoss:
+    """PandaSim.policy_loss' result, device tensors.  Per cloud: sums [B, 5]
+    f64 (the NLL; |head - target| of the start offsets, the end offsets, the
+    start quaternions, the end quaternions), counts [B, 4] i32 (the labelled
+    points, those whose true class is in the start set, in the end set, those
+    predicted right) and confusion [B, nc, nc] i32 (true x predicted; None
+    unless asked for).  Over the batch, f64 scalars:
+        cls_loss    = sum of the NLL / labelled points (F.nll_loss' mean),
+        offset_loss = the two offset sums / (3 * (start rows + end rows)),
+        rot_loss    = the two quaternion sums / (4 * (start rows + end rows)),
+        accuracy    = points predicted right / labelled points.
+    The reference ships the loss modules but no script that calls them: these
+    means, L1Loss' mean over the elements of the sets' rows, are this
+    package's definition.  A batch without a labelled point (a row of either
+    set) gives NaN there."""
+
+    __slots__ = ("sums", "counts", "confusion", "cls_loss", "offset_loss", "rot_loss", "accuracy")
+
+
+class PolicyEvaluation:
+    """PandaSim.evaluate_policy's result: head [B, N, nc + 14], labels (a
+    CloudLabels), loss (a PolicyLoss), decoded (a DecodedWaypoints) and
+    waypoint_error [B, 2] f32, the distance of each decoded waypoint from the
+    true one (NaN where the predicted set is empty)."""
+
+    __slots__ = ("head", "labels", "loss", "decoded", "waypoint_error")
+
+
+def waypoint_labels_args(num_envs: int, points, waypoints, quats, radius, group, count):
+    """label_cloud's argument checks (ValueError), on tensors of any device:
+    -> N and the radius as a float."""
+    B, fn = int(num_envs), "label_cloud"
+    _want(fn, "points", points, (B, "N", 3))
+    N = int(points.shape[1])
+    most = L.CLOUD_MAX_DENSE_POINTS if group is not None else L.CLOUD_MAX_POINTS
+    if not 1 <= N <= most:
+        raise ValueError(f"{fn}: N = {N} points (1 to {L.CLOUD_MAX_POINTS}; to {L.CLOUD_MAX_DENSE_POINTS} with a "
+                         f"group that holds the normalisation)")
+    _want(fn, "waypoints", waypoints, (B, 2, 3))
+    _want(fn, "quats", quats, (B, 2, 4))
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or \
+            not 0.0 < float(radius) < math.inf:
+        raise ValueError(f"{fn}: radius = {radius!r} must be positive and finite")
+    if group is not None:
+        if not all(hasattr(group, a) for a in ("xyz", "centroid", "scale")) or group.centroid is None:
+            raise ValueError(f"{fn}: group must hold xyz, centroid and scale (a GroupedCloud of normalize=True)")
+        _want(fn, "group.xyz", group.xyz, (B, N, 3))
+        _want(fn, "group.centroid", group.centroid, (B, 3))
+        _want(fn, "group.scale", group.scale, (B,))
+    if count is not None:
+        _want(fn, "count", count, (B,), torch.int32)
+    return N, float(radius)
+
+
+def policy_loss_args(num_envs: int, head, cls, target, num_classes, start_classes, end_classes):
+    """policy_loss' argument checks (ValueError), on tensors of any device:
+    -> N, ld, num_classes, the target's row length and the two class masks."""
+    B, fn = int(num_envs), "policy_loss"
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or \
+            not 2 <= num_classes <= L.CLOUD_DECODE_MAX_CLASSES:
+        raise ValueError(f"{fn}: num_classes = {num_classes!r} (a whole number from 2 to "
+                         f"{L.CLOUD_DECODE_MAX_CLASSES})")
+    nc = int(num_classes)
+    _want(fn, "head", head, (B, "N", "ld"))
+    N, ld = int(head.shape[1]), int(head.shape[2])
+    if not 1 <= N <= L.CLOUD_MAX_DENSE_POINTS:
+        raise ValueError(f"{fn}: N = {N} points (1 to {L.CLOUD_MAX_DENSE_POINTS})")
+    if not nc + L.CLOUD_LABEL_COLUMNS <= ld <= L.CLOUD_DECODE_MAX_LD:
+        raise ValueError(f"{fn}: head rows of {ld} columns (num_classes + 14 = {nc + 14} to {L.CLOUD_DECODE_MAX_LD})")
+    _want(fn, "cls", cls, (B, N), torch.int32)
+    _want(fn, "target", target, (B, N, L.CLOUD_LABEL_COLUMNS))
+    try:
+        masks = (_class_mask("start_classes", start_classes, nc), _class_mask("end_classes", end_classes, nc))
+    except ValueError as e:
+        raise ValueError(str(e).replace("decode_waypoints", fn, 1)) from None
+    return N, ld, nc, int(target.shape[2]), masks
+
+
+def demonstration_records(points, colors, keypoint, waypoints, quats, cls, label="pour", count=None):
+    """The B dicts record() saves (generate_combined_dset.py:483), from
+    point_cloud()'s and label_cloud()'s tensors -- host side, off the hot path:
+    np.save(path, records[b]) writes a file the reference's PourDataset reads.
+
+    points [B, N, 3], colors [B, N, 3], keypoint [B, N] (the conditioning
+    channel) or None, waypoints [B, 2, 3], quats [B, 2, 4], cls [B, N]; tensors
+    of any device or arrays.  label one string or B of them.  count None or
+    [B]: a cloud whose count is 0 has no points.  Each dict holds xyz [M, 3]
+    f64, xyz_color [M, 3] f64 (the values given, 0..255 for point_cloud()'s),
+    xyz_kpt [M] f64 (zeros without keypoint), start_waypoint and end_waypoint
+    [3] f64, cls [M] f64, start_ori and end_ori [4] f64 xyzw, label."""
+    def host(a, dtype=np.float64):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return a.astype(dtype)
+
+    pts, col, wp, q, cl = host(points), host(colors), host(waypoints), host(quats), host(cls)
+    B = pts.shape[0]
+    if pts.ndim != 3 or pts.shape[2] != 3 or col.shape != pts.shape or wp.shape != (B, 2, 3) or \
+            q.shape != (B, 2, 4) or cl.shape != pts.shape[:2]:
+        raise ValueError(f"demonstration_records: points [B, N, 3], colors [B, N, 3], waypoints [B, 2, 3], quats "
+                         f"[B, 2, 4], cls [B, N]; got {pts.shape}, {col.shape}, {wp.shape}, {q.shape}, {cl.shape}")
+    kp = np.zeros(pts.shape[:2]) if keypoint is None else host(keypoint)
+    if kp.shape != pts.shape[:2]:
+        raise ValueError(f"demonstration_records: keypoint must be [B, N], got {kp.shape}")
+    labels = [label] * B if isinstance(label, str) else list(label)
+    if len(labels) != B:
+        raise ValueError(f"demonstration_records: {len(labels)} labels for {B} clouds")
+    cnt = None if count is None else host(count, np.int64).reshape(-1)
+    if cnt is not None and cnt.shape != (B,):
+        raise ValueError(f"demonstration_records: count must be [B], got {cnt.shape}")
+    out = []
+    for b in range(B):
+        m = pts.shape[1] if cnt is None or cnt[b] > 0 else 0
+        out.append({"xyz": pts[b, :m].copy(), "xyz_color": col[b, :m].copy(), "xyz_kpt": kp[b, :m].copy(),
+                    "start_waypoint": wp[b, 0].copy(), "end_waypoint": wp[b, 1].copy(), "cls": cl[b, :m].copy(),
+                    "start_ori": q[b, 0].copy(), "end_ori": q[b, 1].copy(), "label": labels[b]})
+    return out
 
 
 _BN_KEYS = ("weight", "bias", "running_mean", "running_var")

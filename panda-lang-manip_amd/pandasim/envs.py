@@ -257,6 +257,23 @@ class PandaVecEnv:
         (PandaSim.predict_waypoints)."""
         return self.sim.predict_waypoints(net, points, colors, seed)
 
+    def label_cloud(self, points, waypoints, quats, radius: float = 0.125, group=None, count=None):
+        """The per-point classes and targets a demonstration's waypoints give
+        every env's cloud (PandaSim.label_cloud)."""
+        return self.sim.label_cloud(points, waypoints, quats, radius, group, count)
+
+    def policy_loss(self, head, cls, target, num_classes, start_classes=(1, 3), end_classes=(2, 3),
+                    return_confusion: bool = False):
+        """The forward value of the policy's losses and its accuracy against
+        label_cloud's targets (PandaSim.policy_loss)."""
+        return self.sim.policy_loss(head, cls, target, num_classes, start_classes, end_classes, return_confusion)
+
+    def evaluate_policy(self, net, points, colors, waypoints, quats, radius: float = 0.125, seed: int = 0,
+                        count=None):
+        """A network against a demonstration: labels, losses, decoded
+        waypoints and their error (PandaSim.evaluate_policy)."""
+        return self.sim.evaluate_policy(net, points, colors, waypoints, quats, radius, seed, count)
+
     def close(self) -> None:
         self.sim.close()
 

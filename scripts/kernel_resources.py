@@ -94,7 +94,7 @@ def main(argv):
                                                  "motion_*.o")) +
                           [os.path.join(ROOT, "panda-lang-manip_amd", "pandasim", "build", "libpandasim", n)
                            for n in ("render_kernels.o", "cloud_kernels.o", "group_kernels.o", "propagate_kernels.o", "mlp_kernels.o", "decode_kernels.o",
-                                     "keypoint_kernels.o")])
+                                     "keypoint_kernels.o", "label_kernels.o")])
     table = {}
     with tempfile.TemporaryDirectory() as tmp:
         for p in paths:
